@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd $REPO
 export BENCH_INDEX_DIR=/tmp/b100
 
-timeout 1750 python3 bench.py --workload bkt_100m_d100_i8_cos \
+timeout 1750 python3 bench.py --full --workload bkt_100m_d100_i8_cos \
     --steps 20 --warmup 5 > "$OUT/f_100m_bench.log" 2>&1
 grep -E "sweep|built|uploaded|truth|baseline|\{" "$OUT/f_100m_bench.log" | tail -16 | tee "$OUT/f_summary.txt"
 

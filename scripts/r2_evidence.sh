@@ -2,6 +2,8 @@
 # Round-2 evidence pass over a PREBUILT index folder (rocprofv3 per the
 # guide: PMC passes separate from trace passes; run from /tmp).
 #   usage: WORKLOAD=... IDX=... MC=... QFILE=... bash scripts/r2_evidence.sh
+# The default IDX/QFILE are what a `bench.py --full` run saves (its CPU
+# baseline leg writes the index folder and the query file).
 set -x
 cd /tmp && export TMPDIR=/tmp
 REPO=/root/repo
