@@ -24,6 +24,8 @@
 #include <algorithm>
 #include <cctype>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -34,6 +36,68 @@ using namespace sptag_amd;
 
 namespace {
 
+/* Every device allocation of the host code lives in one of these, so any
+ * early return releases it. Move-only; frees in the destructor. An empty
+ * buffer makes no HIP call, so a handle created on a machine without a GPU
+ * is freed without touching the runtime. */
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = o.p_; cap_ = o.cap_;
+            o.p_ = nullptr; o.cap_ = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    /* drop the old block, then allocate exactly `bytes` */
+    hipError_t alloc(size_t bytes)
+    {
+        reset();
+        hipError_t e = hipMalloc(&p_, bytes);
+        if (e == hipSuccess) cap_ = bytes; else p_ = nullptr;
+        return e;
+    }
+    /* grow-only: a block that is already large enough is kept */
+    hipError_t ensure(size_t bytes) { return cap_ >= bytes ? hipSuccess : alloc(bytes); }
+    template <class T = void> T* as() const { return static_cast<T*>(p_); }
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    void* p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+/* the start/stop event pair that times a kernel pass; created on first use */
+struct DevEvents {
+    hipEvent_t start = nullptr, stop = nullptr;
+    DevEvents() = default;
+    DevEvents(const DevEvents&) = delete;
+    DevEvents& operator=(const DevEvents&) = delete;
+    ~DevEvents()
+    {
+        if (start) (void)hipEventDestroy(start);
+        if (stop) (void)hipEventDestroy(stop);
+    }
+    void ensure()
+    {
+        if (!start) { (void)hipEventCreate(&start); (void)hipEventCreate(&stop); }
+    }
+};
+
 struct HostIndex {
     int device = 0;
     int algo = ALGO_BKT;
@@ -42,40 +106,29 @@ struct HostIndex {
     int32_t default_maxcheck = DEFAULT_MAXCHECK;
     int32_t init_pivots = INIT_PIVOTS, other_pivots = OTHER_PIVOTS;
     int32_t nobetter_threshold = 3;  /* KDT ParameterDefinitionList */
-    bool refine_mode = false;  /* internal: RefineSearchIndex dispatch flags */
     bool has_deleted = false;
-    /* device allocations */
-    void* d_vectors = nullptr;
-    int32_t* d_graph = nullptr;
-    int32_t* d_tree = nullptr;
-    int32_t* d_tree_start = nullptr;
-    uint8_t* d_deleted = nullptr;
+    /* the index on the device */
+    DevBuf d_vectors, d_graph, d_tree, d_tree_start, d_deleted;
     /* host copies kept for save_index and shard assembly */
     std::vector<char> h_vectors;
     std::vector<int32_t> h_graph, h_tree, h_tree_start;
     std::vector<uint8_t> h_deleted;
     int64_t deleted_count = 0;
     std::mutex lock;
-    /* cached per-handle search scratch (grown on demand) */
-    int32_t* d_visited = nullptr; size_t visited_cap = 0;
-    int32_t* d_oflow = nullptr;   size_t oflow_cap = 0;
-    int32_t* d_stats = nullptr;   size_t stats_cap = 0;
-    void* d_gng = nullptr;        size_t gng_cap = 0;
-    void* d_gspt = nullptr;       size_t gspt_cap = 0;
-    void* d_redo = nullptr;       size_t redo_cap = 0;
-    void* d_gspt0 = nullptr;      size_t gspt0_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    /* cached per-handle search scratch (grow-only) */
+    DevBuf d_visited, d_oflow, d_stats, d_gng, d_gspt, d_redo, d_gspt0;
+    DevEvents ev;
     double last_kernel_ms = 0;
     long long last_checked = 0, last_popped = 0;
 
     size_t esz() const { return vt == VT_FLOAT ? 4 : 1; }
     DevIndex dev() const {
         DevIndex di;
-        di.vectors = d_vectors;
-        di.graph = d_graph;
-        di.tree_nodes = d_tree;
-        di.tree_start = d_tree_start;
-        di.deleted = d_deleted;
+        di.vectors = d_vectors.as();
+        di.graph = d_graph.as<int32_t>();
+        di.tree_nodes = d_tree.as<int32_t>();
+        di.tree_start = d_tree_start.as<int32_t>();
+        di.deleted = d_deleted.as<uint8_t>();
         di.n = n; di.dim = dim; di.deg = deg; di.ntrees = ntrees;
         di.n_tree_nodes = n_tree_nodes;
         di.has_deleted = has_deleted ? 1 : 0;
@@ -93,6 +146,15 @@ struct HostIndex {
             return ret;                                                     \
         }                                                                   \
     } while (0)
+
+/* allocate `b` at `bytes` and fill it from host memory */
+int dev_upload(DevBuf& b, const void* src, size_t bytes)
+{
+    HIP_OR_FAIL(b.alloc(bytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(hipMemcpy(b.as(), src, bytes, hipMemcpyHostToDevice),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
 
 bool read_file(const std::string& path, std::vector<char>& out)
 {
@@ -160,25 +222,17 @@ bool ini_get(const std::string& text, const char* section, const char* key,
 int upload(HostIndex* ix)
 {
     HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMalloc(&ix->d_vectors, ix->h_vectors.size()), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(ix->d_vectors, ix->h_vectors.data(), ix->h_vectors.size(),
-                          hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMalloc(&ix->d_graph, ix->h_graph.size() * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(ix->d_graph, ix->h_graph.data(), ix->h_graph.size() * 4,
-                          hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMalloc(&ix->d_tree, ix->h_tree.size() * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(ix->d_tree, ix->h_tree.data(), ix->h_tree.size() * 4,
-                          hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMalloc(&ix->d_tree_start, ix->h_tree_start.size() * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(ix->d_tree_start, ix->h_tree_start.data(),
-                          ix->h_tree_start.size() * 4, hipMemcpyHostToDevice),
-                SPTAG_AMD_ERR_NOGPU);
-    if (ix->has_deleted) {
-        HIP_OR_FAIL(hipMalloc(&ix->d_deleted, ix->h_deleted.size()), SPTAG_AMD_ERR_OOM);
-        HIP_OR_FAIL(hipMemcpy(ix->d_deleted, ix->h_deleted.data(), ix->h_deleted.size(),
-                              hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-    }
-    return SPTAG_AMD_OK;
+    int rc = dev_upload(ix->d_vectors, ix->h_vectors.data(), ix->h_vectors.size());
+    if (rc == SPTAG_AMD_OK)
+        rc = dev_upload(ix->d_graph, ix->h_graph.data(), ix->h_graph.size() * 4);
+    if (rc == SPTAG_AMD_OK)
+        rc = dev_upload(ix->d_tree, ix->h_tree.data(), ix->h_tree.size() * 4);
+    if (rc == SPTAG_AMD_OK)
+        rc = dev_upload(ix->d_tree_start, ix->h_tree_start.data(),
+                        ix->h_tree_start.size() * 4);
+    if (rc == SPTAG_AMD_OK && ix->has_deleted)
+        rc = dev_upload(ix->d_deleted, ix->h_deleted.data(), ix->h_deleted.size());
+    return rc;
 }
 
 uint32_t next_pow2(uint32_t x)
@@ -188,9 +242,91 @@ uint32_t next_pow2(uint32_t x)
     return p;
 }
 
+/* read cursor over a file's bytes: take() refuses to run past the end */
+struct Cursor {
+    const char* p;
+    size_t left;
+    explicit Cursor(const std::vector<char>& b) : p(b.data()), left(b.size()) {}
+    const char* take(size_t bytes)
+    {
+        if (bytes > left) return nullptr;
+        const char* r = p;
+        p += bytes;
+        left -= bytes;
+        return r;
+    }
+    bool i32(int32_t& v)
+    {
+        const char* s = take(4);
+        if (s) memcpy(&v, s, 4);
+        return s != nullptr;
+    }
+};
+
+struct Part { const void* p; size_t n; };
+
+/* write the parts back to back; false on any short write */
+bool write_file(const std::string& path, std::initializer_list<Part> parts)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    bool ok = true;
+    for (const Part& s : parts)
+        ok = ok && (s.n == 0 || fwrite(s.p, 1, s.n, f) == s.n);
+    return fclose(f) == 0 && ok;
+}
+
 }  // namespace
 
 struct SptagAmdIndex : HostIndex {};
+
+/* The one place that validates arguments and builds a handle; `tree_nodes`
+ * holds 3 int32 per node for BKT and 4 for KDT. */
+static SptagAmdIndex* create_index(int algo, int32_t n, int32_t dim, int valuetype,
+                                   int distmethod, const void* vectors,
+                                   int32_t ntrees, const int32_t* tree_start,
+                                   int32_t n_tree_nodes, const int32_t* tree_nodes,
+                                   int32_t degree, const int32_t* graph,
+                                   const uint8_t* deleted, int device)
+{
+    if (n <= 0 || dim <= 0 || dim > MAX_DIM || degree <= 0 || degree > MAX_DEG ||
+        ntrees <= 0 || n_tree_nodes <= 0)
+        return nullptr;
+    if (valuetype == SPTAG_AMD_VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) {
+        /* beyond this the int8 distances stop being exact integers in float */
+        fprintf(stderr, "sptag_amd: int8 dim %d exceeds exact-float range\n", dim);
+        return nullptr;
+    }
+    std::unique_ptr<SptagAmdIndex> ix(new SptagAmdIndex());
+    ix->device = device;
+    ix->algo = algo;
+    ix->vt = valuetype;
+    ix->dm = distmethod;
+    ix->n = n; ix->dim = dim; ix->deg = degree;
+    ix->ntrees = ntrees;
+    ix->h_vectors.assign((const char*)vectors,
+                         (const char*)vectors + (size_t)n * dim * ix->esz());
+    ix->h_graph.assign(graph, graph + (size_t)n * degree);
+    ix->h_tree_start.assign(tree_start, tree_start + ntrees);
+    const size_t width = algo == ALGO_KDT ? 4 : 3;
+    ix->h_tree.assign(tree_nodes, tree_nodes + (size_t)n_tree_nodes * width);
+    /* BKTree.h:683: append sentinel if the stored array does not end with
+     * centerid == -1 */
+    if (algo == ALGO_BKT && ix->h_tree[(size_t)(n_tree_nodes - 1) * 3] != -1) {
+        ix->h_tree.insert(ix->h_tree.end(), 3, -1);
+        n_tree_nodes += 1;
+    }
+    ix->n_tree_nodes = n_tree_nodes;
+    if (deleted) {
+        ix->h_deleted.assign(deleted, deleted + n);
+        for (int32_t i = 0; i < n; i++) ix->deleted_count += deleted[i] ? 1 : 0;
+        ix->has_deleted = ix->deleted_count > 0;
+    }
+    /* without a GPU the handle still supports metadata queries + save_index;
+     * search fails with ERR_NOGPU. */
+    if (sptag_amd_gpu_available() && upload(ix.get()) != SPTAG_AMD_OK) return nullptr;
+    return ix.release();
+}
 
 extern "C" {
 
@@ -212,45 +348,9 @@ SptagAmdIndex* sptag_amd_create_index(int32_t n, int32_t dim, int valuetype,
                                       int32_t degree, const int32_t* graph,
                                       const uint8_t* deleted, int device)
 {
-    if (n <= 0 || dim <= 0 || dim > MAX_DIM || degree <= 0 || degree > MAX_DEG ||
-        ntrees <= 0 || n_tree_nodes <= 0)
-        return nullptr;
-    if (valuetype == SPTAG_AMD_VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) {
-        fprintf(stderr, "sptag_amd: int8 dim %d exceeds exact-float range\n", dim);
-        return nullptr;
-    }
-    auto* ix = new SptagAmdIndex();
-    ix->device = device;
-    ix->vt = valuetype;
-    ix->dm = distmethod;
-    ix->n = n; ix->dim = dim; ix->deg = degree;
-    ix->ntrees = ntrees;
-    ix->h_vectors.assign((const char*)vectors,
-                         (const char*)vectors + (size_t)n * dim * ix->esz());
-    ix->h_graph.assign(graph, graph + (size_t)n * degree);
-    ix->h_tree_start.assign(tree_start, tree_start + ntrees);
-    ix->h_tree.assign(tree_nodes, tree_nodes + (size_t)n_tree_nodes * 3);
-    /* BKTree.h:683: append sentinel if the stored array does not end with
-     * centerid == -1 */
-    if (ix->h_tree[(size_t)(n_tree_nodes - 1) * 3] != -1) {
-        ix->h_tree.push_back(-1); ix->h_tree.push_back(-1); ix->h_tree.push_back(-1);
-        n_tree_nodes += 1;
-    }
-    ix->n_tree_nodes = n_tree_nodes;
-    if (deleted) {
-        ix->h_deleted.assign(deleted, deleted + n);
-        for (int32_t i = 0; i < n; i++) ix->deleted_count += deleted[i] ? 1 : 0;
-        ix->has_deleted = ix->deleted_count > 0;
-    }
-    if (sptag_amd_gpu_available()) {
-        if (upload(ix) != SPTAG_AMD_OK) {
-            sptag_amd_free_index(ix);
-            return nullptr;
-        }
-    }
-    /* without a GPU the handle still supports metadata queries + save_index;
-     * search fails with ERR_NOGPU. */
-    return ix;
+    return create_index(ALGO_BKT, n, dim, valuetype, distmethod, vectors, ntrees,
+                        tree_start, n_tree_nodes, tree_nodes, degree, graph,
+                        deleted, device);
 }
 
 SptagAmdIndex* sptag_amd_create_index_kdt(int32_t n, int32_t dim, int valuetype,
@@ -260,41 +360,9 @@ SptagAmdIndex* sptag_amd_create_index_kdt(int32_t n, int32_t dim, int valuetype,
                                           int32_t degree, const int32_t* graph,
                                           const uint8_t* deleted, int device)
 {
-    if (n <= 0 || dim <= 0 || dim > MAX_DIM || degree <= 0 || degree > MAX_DEG ||
-        ntrees <= 0 || n_tree_nodes <= 0)
-        return nullptr;
-    if (valuetype == SPTAG_AMD_VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) {
-        /* same exact-float-range guard as the BKT create path: beyond it the
-         * int8 distances stop being exact integers in float. */
-        fprintf(stderr, "sptag_amd: int8 dim %d exceeds exact-float range\n", dim);
-        return nullptr;
-    }
-    auto* ix = new SptagAmdIndex();
-    ix->device = device;
-    ix->algo = ALGO_KDT;
-    ix->vt = valuetype;
-    ix->dm = distmethod;
-    ix->n = n; ix->dim = dim; ix->deg = degree;
-    ix->ntrees = ntrees;
-    ix->n_tree_nodes = n_tree_nodes;
-    ix->h_vectors.assign((const char*)vectors,
-                         (const char*)vectors + (size_t)n * dim * ix->esz());
-    ix->h_graph.assign(graph, graph + (size_t)n * degree);
-    ix->h_tree_start.assign(tree_start, tree_start + ntrees);
-    const int32_t* kw = (const int32_t*)kdt_nodes;
-    ix->h_tree.assign(kw, kw + (size_t)n_tree_nodes * 4);
-    if (deleted) {
-        ix->h_deleted.assign(deleted, deleted + n);
-        for (int32_t i = 0; i < n; i++) ix->deleted_count += deleted[i] ? 1 : 0;
-        ix->has_deleted = ix->deleted_count > 0;
-    }
-    if (sptag_amd_gpu_available()) {
-        if (upload(ix) != SPTAG_AMD_OK) {
-            sptag_amd_free_index(ix);
-            return nullptr;
-        }
-    }
-    return ix;
+    return create_index(ALGO_KDT, n, dim, valuetype, distmethod, vectors, ntrees,
+                        tree_start, n_tree_nodes, (const int32_t*)kdt_nodes, degree,
+                        graph, deleted, device);
 }
 
 SptagAmdIndex* sptag_amd_load_index(const char* folder, int device)
@@ -341,33 +409,40 @@ SptagAmdIndex* sptag_amd_load_index(const char* folder, int device)
         return nullptr;
     bool have_del = read_file(dir + "deletes.bin", db);
 
-    const int32_t* vh = (const int32_t*)vb.data();
-    int32_t n = vh[0], dim = vh[1];
-    const int32_t* th = (const int32_t*)tb.data();
-    int32_t ntrees = th[0];
-    const int32_t* tstart = th + 1;
-    int32_t nnodes = th[1 + ntrees];
-    const int32_t* tnodes = th + 2 + ntrees;
-    const int32_t* gh = (const int32_t*)gb.data();
-    int32_t gn = gh[0], deg = gh[1];
+    /* every header field and body is taken through a cursor, so a short or
+     * empty file is a failed load, never a read past the buffer */
+    Cursor vc(vb), tc(tb), gc(gb);
+    int32_t n = 0, dim = 0, ntrees = 0, nnodes = 0, gn = 0, deg = 0;
+    const char *vecs = nullptr, *tstart = nullptr, *tnodes = nullptr, *adj = nullptr;
+    const size_t esz = vt == VT_FLOAT ? 4 : 1, node_bytes = algo == ALGO_KDT ? 16 : 12;
+    auto refuse = [](const char* file) -> SptagAmdIndex* {
+        fprintf(stderr, "sptag_amd: %s is truncated or malformed\n", file);
+        return nullptr;
+    };
+    if (!vc.i32(n) || !vc.i32(dim) || n <= 0 || dim <= 0 || dim > MAX_DIM ||
+        !(vecs = vc.take((size_t)n * dim * esz)))
+        return refuse("vectors.bin");
+    if (!tc.i32(ntrees) || ntrees <= 0 || !(tstart = tc.take((size_t)ntrees * 4)) ||
+        !tc.i32(nnodes) || nnodes <= 0 ||
+        !(tnodes = tc.take((size_t)nnodes * node_bytes)))
+        return refuse("tree.bin");
+    if (!gc.i32(gn) || !gc.i32(deg) || deg <= 0 || deg > MAX_DEG)
+        return refuse("graph.bin");
     if (gn != n) {
         fprintf(stderr, "sptag_amd: graph rows %d != vectors %d\n", gn, n);
         return nullptr;
     }
+    if (!(adj = gc.take((size_t)n * deg * 4))) return refuse("graph.bin");
     const uint8_t* del = nullptr;
     if (have_del && db.size() >= 12 + (size_t)n) {
         int32_t delcount = ((const int32_t*)db.data())[0];
         if (delcount > 0) del = (const uint8_t*)db.data() + 12;
     }
 
-    SptagAmdIndex* ix;
-    if (algo == ALGO_BKT)
-        ix = sptag_amd_create_index(n, dim, vt, dm, vb.data() + 8, ntrees, tstart,
-                                    nnodes, tnodes, deg, gh + 2, del, device);
-    else
-        ix = sptag_amd_create_index_kdt(n, dim, vt, dm, vb.data() + 8, ntrees,
-                                        tstart, nnodes, tnodes, deg, gh + 2, del,
-                                        device);
+    SptagAmdIndex* ix = create_index(algo, n, dim, vt, dm, vecs, ntrees,
+                                     (const int32_t*)tstart, nnodes,
+                                     (const int32_t*)tnodes, deg,
+                                     (const int32_t*)adj, del, device);
     if (!ix) return nullptr;
     if (ini_get(ini, "Index", "ThresholdOfNumberOfContinuousNoBetterPropagation", val))
         ix->nobetter_threshold = atoi(val.c_str());
@@ -386,42 +461,17 @@ SptagAmdIndex* sptag_amd_load_index(const char* folder, int device)
 
 void sptag_amd_free_index(SptagAmdIndex* ix)
 {
-    if (!ix) return;
-    if (ix->d_vectors) (void)hipFree(ix->d_vectors);
-    if (ix->d_graph) (void)hipFree(ix->d_graph);
-    if (ix->d_tree) (void)hipFree(ix->d_tree);
-    if (ix->d_tree_start) (void)hipFree(ix->d_tree_start);
-    if (ix->d_deleted) (void)hipFree(ix->d_deleted);
-    if (ix->d_visited) (void)hipFree(ix->d_visited);
-    if (ix->d_oflow) (void)hipFree(ix->d_oflow);
-    if (ix->d_stats) (void)hipFree(ix->d_stats);
-    if (ix->d_gng) (void)hipFree(ix->d_gng);
-    if (ix->d_gspt) (void)hipFree(ix->d_gspt);
-    if (ix->d_redo) (void)hipFree(ix->d_redo);
-    if (ix->d_gspt0) (void)hipFree(ix->d_gspt0);
-    if (ix->ev0) (void)hipEventDestroy(ix->ev0);
-    if (ix->ev1) (void)hipEventDestroy(ix->ev1);
-    delete ix;
+    if (ix) delete ix;   /* the owners on the handle release the device side */
 }
 
-static int ensure_cap(void** p, size_t* cap, size_t need)
+/* SearchCfg fields that the one-shot search and the iterator share: pivots,
+ * threshold, dispatch flags, DistPriorityQueue size and the speculation
+ * knob. `refine` selects the RefineSearchIndex dispatch (search_dup=0,
+ * search_deleted=1) of the add path; the SearchIndex(QueryResult&,bool)
+ * defaults otherwise. Heap and visited capacities are the caller's. */
+static SearchCfg base_cfg(const SptagAmdIndex* ix, int32_t nq, int32_t k,
+                          int32_t max_check, bool refine)
 {
-    if (*cap >= need) return SPTAG_AMD_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need) != hipSuccess) return SPTAG_AMD_ERR_OOM;
-    *cap = need;
-    return SPTAG_AMD_OK;
-}
-
-/* core search on DEVICE buffers; scratch cached on the handle. */
-static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
-                              int32_t k, int32_t max_check,
-                              int32_t* d_vids, float* d_dists)
-{
-    if (max_check <= 0) max_check = ix->default_maxcheck;
-
     SearchCfg cfg;
     cfg.nq = nq;
     cfg.k = k;
@@ -429,10 +479,101 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
     cfg.init_pivots = ix->init_pivots;
     cfg.other_pivots = ix->other_pivots;
     cfg.nobetter_threshold = ix->nobetter_threshold;
-    cfg.search_dup = 1;        /* SearchIndex(QueryResult&,bool) defaults */
-    cfg.search_deleted = 0;
-    if (ix->refine_mode) { cfg.search_dup = 0; cfg.search_deleted = 1; }
+    cfg.search_dup = refine ? 0 : 1;
+    cfg.search_deleted = refine ? 1 : 0;
     cfg.dpq_cap = std::max(max_check / 16, k);   /* WorkSpace.h:268 */
+    cfg.vcap = cfg.ng_cap = cfg.spt_cap = 0;
+    /* measured on MI355X (profiles/round2_experiments/ab_v5.txt): both
+     * speculation forms LOSE throughput at 10M/mc2048 (745k QPS off vs 622k
+     * on) — the extra touch loads consume request bandwidth the resident
+     * waves already saturate. Off by default; kept for experiments. */
+    cfg.spec_flags = 0;
+    if (const char* e = getenv("SPTAG_AMD_SPEC")) cfg.spec_flags = atoi(e);
+    cfg.prof = 0;
+    return cfg;
+}
+
+/* host copies of one pass's per-query stats and overflow flags */
+struct PassOut {
+    int sstride;
+    std::vector<int32_t> stats, oflow;
+    PassOut(int stride, int32_t nq)
+        : sstride(stride), stats((size_t)stride * nq), oflow(nq) {}
+};
+
+/* One kernel pass over cfg.nq queries: zero the visited tables, launch
+ * between the two events, sync, read back stats and overflow flags, and add
+ * the time and the counters of the queries that did not overflow to the
+ * handle's last_* figures. With `d_idx` the pass ran on gathered rows, and
+ * its results are scattered to d_vids/d_dists before the one sync. */
+static int run_pass(SptagAmdIndex* ix, bool heaps_in_lds, const SearchCfg& cfg,
+                    const SearchBufs& bufs, PassOut& out,
+                    const int32_t* d_idx = nullptr, int32_t* d_vids = nullptr,
+                    float* d_dists = nullptr)
+{
+    const int32_t nq = cfg.nq;
+    HIP_OR_FAIL(hipMemsetAsync(bufs.visited, 0, (size_t)nq * cfg.vcap * 4),
+                SPTAG_AMD_ERR_NOGPU);
+    (void)hipEventRecord(ix->ev.start);
+    int err = launch_bkt_search(ix->vt, ix->dm, heaps_in_lds, ix->dev(), cfg, bufs,
+                                nullptr);
+    if (err != 0) {
+        fprintf(stderr, "sptag_amd: %slaunch failed %d\n",
+                heaps_in_lds ? "" : "global-variant ", err);
+        return SPTAG_AMD_ERR_INTERNAL;
+    }
+    (void)hipEventRecord(ix->ev.stop);
+    if (d_idx) {
+        launch_scatter_rows(d_vids, bufs.out_vids, cfg.k * 4, d_idx, nq, nullptr);
+        launch_scatter_rows(d_dists, bufs.out_dists, cfg.k * 4, d_idx, nq, nullptr);
+    }
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ix->ev.start, ix->ev.stop);
+    ix->last_kernel_ms += ms;
+    HIP_OR_FAIL(hipMemcpy(out.oflow.data(), bufs.oflow, (size_t)nq * 4,
+                          hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out.stats.data(), bufs.stats, (size_t)nq * out.sstride * 4,
+                          hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
+    for (int32_t i = 0; i < nq; i++) {
+        if (out.oflow[i]) continue;
+        ix->last_checked += out.stats[(size_t)out.sstride * i];
+        ix->last_popped += out.stats[(size_t)out.sstride * i + 1];
+    }
+    return SPTAG_AMD_OK;
+}
+
+/* SPTAG_AMD_PROF: per-phase cycle sums of one LDS pass (BKT kernels only) */
+static void prof_dump(const PassOut& out, int32_t nq, double ms)
+{
+    static const char* pname[10] = {
+        "seed", "pop", "row", "serial", "cas",
+        "dist", "insert", "tree", "spec", "sort"};
+    double tot[10] = {};
+    for (int32_t i = 0; i < nq; i++)
+        for (int p = 0; p < 10; p++)
+            tot[p] += (double)out.stats[(size_t)out.sstride * i + 2 + p];
+    double all = 0;
+    for (int p = 0; p < 10; p++) all += tot[p];
+    fprintf(stderr, "sptag_amd PROF (sum of per-query wave cycles, "
+                    "%d queries, kernel %.2f ms):\n", nq, ms);
+    for (int p = 0; p < 10; p++)
+        fprintf(stderr, "  %-7s %14.0f  (%5.1f%%)\n", pname[p], tot[p],
+                all > 0 ? 100.0 * tot[p] / all : 0.0);
+    double ngi = 0;
+    for (int32_t i = 0; i < nq; i++)
+        ngi += (double)out.stats[(size_t)out.sstride * i + 12];
+    fprintf(stderr, "  (insert = ng-heap %14.0f + results-set rest)\n", ngi);
+}
+
+/* core search on DEVICE buffers; scratch cached on the handle. */
+static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
+                              int32_t k, int32_t max_check,
+                              int32_t* d_vids, float* d_dists, bool refine = false)
+{
+    if (max_check <= 0) max_check = ix->default_maxcheck;
+
+    SearchCfg cfg = base_cfg(ix, nq, k, max_check, refine);
     /* k-deep (refine-class) searches keep expanding far past MaxCheck —
      * the budget is only consulted when a pop misses the k-deep results
      * queue (BKTIndex.cpp:326) — so the visited table must scale with k
@@ -451,12 +592,6 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
     if (const char* e = getenv("SPTAG_AMD_NG_CAP"))   /* perf experiments */
         cfg.ng_cap = std::max(256, atoi(e));
     cfg.spt_cap = 4096;
-    /* measured on MI355X (gpurun_out/ab_v5.txt): both speculation forms
-     * LOSE throughput at 10M/mc2048 (745k QPS off vs 622k on) — the extra
-     * touch loads consume request bandwidth the resident waves already
-     * saturate. Off by default; kept for experiments. */
-    cfg.spec_flags = 0;
-    if (const char* e = getenv("SPTAG_AMD_SPEC")) cfg.spec_flags = atoi(e);
     /* phase-cycle diagnostic (BKT kernels only — the KDT kernel writes
      * plain stride-2 stats) */
     cfg.prof = (getenv("SPTAG_AMD_PROF") && ix->algo == ALGO_BKT) ? 1 : 0;
@@ -467,84 +602,35 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
                                 ix->device);
     bool lds_ok = lds_bytes(ix->dim, ix->esz(), cfg, true) <= (size_t)lds_limit;
 
-    if (ensure_cap((void**)&ix->d_visited, &ix->visited_cap,
-                   (size_t)nq * cfg.vcap * 4) != SPTAG_AMD_OK) return SPTAG_AMD_ERR_OOM;
-    if (ensure_cap((void**)&ix->d_oflow, &ix->oflow_cap, (size_t)nq * 4) != SPTAG_AMD_OK)
-        return SPTAG_AMD_ERR_OOM;
-    if (ensure_cap((void**)&ix->d_stats, &ix->stats_cap,
-                   (size_t)nq * sstride * 4) != SPTAG_AMD_OK)
-        return SPTAG_AMD_ERR_OOM;
-    if (!ix->ev0) { (void)hipEventCreate(&ix->ev0); (void)hipEventCreate(&ix->ev1); }
-
-    if (ensure_cap(&ix->d_gspt0, &ix->gspt0_cap,
-                   (size_t)nq * ((size_t)cfg.spt_cap + 1) * 8) != SPTAG_AMD_OK)
-        return SPTAG_AMD_ERR_OOM;
+    HIP_OR_FAIL(ix->d_visited.ensure((size_t)nq * cfg.vcap * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(ix->d_oflow.ensure((size_t)nq * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(ix->d_stats.ensure((size_t)nq * sstride * 4), SPTAG_AMD_ERR_OOM);
+    ix->ev.ensure();
+    HIP_OR_FAIL(ix->d_gspt0.ensure((size_t)nq * ((size_t)cfg.spt_cap + 1) * 8),
+                SPTAG_AMD_ERR_OOM);
 
     SearchBufs bufs;
     bufs.queries = d_q;
     bufs.out_vids = d_vids;
     bufs.out_dists = d_dists;
-    bufs.visited = ix->d_visited;
-    bufs.oflow = ix->d_oflow;
-    bufs.stats = ix->d_stats;
+    bufs.visited = ix->d_visited.as<int32_t>();
+    bufs.oflow = ix->d_oflow.as<int32_t>();
+    bufs.stats = ix->d_stats.as<int32_t>();
     bufs.gheap_ng = nullptr;
-    bufs.gheap_spt = ix->d_gspt0;
+    bufs.gheap_spt = ix->d_gspt0.as();
 
     ix->last_kernel_ms = 0;
     ix->last_checked = 0;
     ix->last_popped = 0;
-    std::vector<int32_t> stats((size_t)sstride * nq);
+    PassOut out(sstride, nq);
     std::vector<int32_t> redo;
     bool all_global = !lds_ok;
     if (lds_ok) {
-        HIP_OR_FAIL(hipMemsetAsync(ix->d_visited, 0, (size_t)nq * cfg.vcap * 4),
-                    SPTAG_AMD_ERR_NOGPU);
-        (void)hipEventRecord(ix->ev0);
-        int err = launch_bkt_search(ix->vt, ix->dm, true, ix->dev(), cfg, bufs, nullptr);
-        if (err != 0) {
-            fprintf(stderr, "sptag_amd: launch failed %d\n", err);
-            return SPTAG_AMD_ERR_INTERNAL;
-        }
-        (void)hipEventRecord(ix->ev1);
-        HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ix->ev0, ix->ev1);
-        ix->last_kernel_ms += ms;
-        std::vector<int32_t> oflow(nq);
-        HIP_OR_FAIL(hipMemcpy(oflow.data(), ix->d_oflow, (size_t)nq * 4,
-                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
-        HIP_OR_FAIL(hipMemcpy(stats.data(), ix->d_stats,
-                              (size_t)nq * sstride * 4,
-                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
-        for (int32_t i = 0; i < nq; i++) {
-            if (oflow[i]) {
-                redo.push_back(i);
-            } else {
-                ix->last_checked += stats[(size_t)sstride * i];
-                ix->last_popped += stats[(size_t)sstride * i + 1];
-            }
-        }
-        if (cfg.prof && ix->algo == ALGO_BKT) {
-            static const char* pname[10] = {
-                "seed", "pop", "row", "serial", "cas",
-                "dist", "insert", "tree", "spec", "sort"};
-            double tot[10] = {};
-            for (int32_t i = 0; i < nq; i++)
-                for (int p = 0; p < 10; p++)
-                    tot[p] += (double)stats[(size_t)sstride * i + 2 + p];
-            double all = 0;
-            for (int p = 0; p < 10; p++) all += tot[p];
-            fprintf(stderr, "sptag_amd PROF (sum of per-query wave cycles, "
-                            "%d queries, kernel %.2f ms):\n", nq, ms);
-            for (int p = 0; p < 10; p++)
-                fprintf(stderr, "  %-7s %14.0f  (%5.1f%%)\n", pname[p], tot[p],
-                        all > 0 ? 100.0 * tot[p] / all : 0.0);
-            double ngi = 0;
-            for (int32_t i = 0; i < nq; i++)
-                ngi += (double)stats[(size_t)sstride * i + 12];
-            fprintf(stderr, "  (insert = ng-heap %14.0f + results-set rest)\n",
-                    ngi);
-        }
+        int rc = run_pass(ix, true, cfg, bufs, out);
+        if (rc != SPTAG_AMD_OK) return rc;
+        for (int32_t i = 0; i < nq; i++)
+            if (out.oflow[i]) redo.push_back(i);
+        if (cfg.prof) prof_dump(out, nq, ix->last_kernel_ms);
         if (!redo.empty() && getenv("SPTAG_AMD_DEBUG"))
             fprintf(stderr, "sptag_amd: %zu/%d queries overflowed (rerun)\n",
                     redo.size(), nq);
@@ -557,76 +643,46 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
     }
 
     int32_t gq_n = all_global ? nq : (int32_t)redo.size();
-    if (gq_n > 0) {
-        SearchCfg c2 = cfg;
-        c2.nq = gq_n;
-        c2.ng_cap = max_check * 30;     /* reference capacities */
-        c2.spt_cap = max_check * 10;
-        if (ensure_cap(&ix->d_gng, &ix->gng_cap,
-                       (size_t)gq_n * ((size_t)c2.ng_cap + 1) * 8) != SPTAG_AMD_OK)
-            return SPTAG_AMD_ERR_OOM;
-        if (ensure_cap(&ix->d_gspt, &ix->gspt_cap,
-                       (size_t)gq_n * ((size_t)c2.spt_cap + 1) * 8) != SPTAG_AMD_OK)
-            return SPTAG_AMD_ERR_OOM;
-        SearchBufs b2 = bufs;
-        b2.gheap_ng = ix->d_gng;
-        b2.gheap_spt = ix->d_gspt;
+    if (gq_n == 0) return SPTAG_AMD_OK;
+    SearchCfg c2 = cfg;
+    c2.nq = gq_n;
+    c2.ng_cap = max_check * 30;     /* reference capacities */
+    c2.spt_cap = max_check * 10;
+    HIP_OR_FAIL(ix->d_gng.ensure((size_t)gq_n * ((size_t)c2.ng_cap + 1) * 8),
+                SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(ix->d_gspt.ensure((size_t)gq_n * ((size_t)c2.spt_cap + 1) * 8),
+                SPTAG_AMD_ERR_OOM);
+    SearchBufs b2 = bufs;
+    b2.gheap_ng = ix->d_gng.as();
+    b2.gheap_spt = ix->d_gspt.as();
+    int32_t* d_idx = nullptr;
+    if (!all_global) {
+        /* compact the flagged queries on-device */
         size_t row = (size_t)ix->dim * ix->esz();
-        if (!all_global) {
-            /* compact the flagged queries on-device */
-            size_t qseg = ((size_t)gq_n * row + 15) & ~15ul;  /* align */
-            size_t need = (size_t)gq_n * 4 + 16 + qseg + (size_t)gq_n * k * 8;
-            if (ensure_cap(&ix->d_redo, &ix->redo_cap, need) != SPTAG_AMD_OK)
-                return SPTAG_AMD_ERR_OOM;
-            int32_t* d_idx = (int32_t*)ix->d_redo;
-            char* d_q2 = (char*)ix->d_redo + (((size_t)gq_n * 4 + 15) & ~15ul);
-            int32_t* d_v2 = (int32_t*)(d_q2 + qseg);
-            float* d_d2 = (float*)(d_v2 + (size_t)gq_n * k);
-            HIP_OR_FAIL(hipMemcpy(d_idx, redo.data(), (size_t)gq_n * 4,
-                                  hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-            launch_gather_rows(d_q2, d_q, (int)row, d_idx, gq_n, nullptr);
-            b2.queries = d_q2;
-            b2.out_vids = d_v2;
-            b2.out_dists = d_d2;
-        }
-        HIP_OR_FAIL(hipMemsetAsync(ix->d_visited, 0, (size_t)gq_n * cfg.vcap * 4),
-                    SPTAG_AMD_ERR_NOGPU);
-        (void)hipEventRecord(ix->ev0);
-        int err = launch_bkt_search(ix->vt, ix->dm, false, ix->dev(), c2, b2, nullptr);
-        if (err != 0) {
-            fprintf(stderr, "sptag_amd: global-variant launch failed %d\n", err);
+        size_t qseg = ((size_t)gq_n * row + 15) & ~15ul;  /* align */
+        size_t need = (size_t)gq_n * 4 + 16 + qseg + (size_t)gq_n * k * 8;
+        HIP_OR_FAIL(ix->d_redo.ensure(need), SPTAG_AMD_ERR_OOM);
+        d_idx = ix->d_redo.as<int32_t>();
+        char* d_q2 = ix->d_redo.as<char>() + (((size_t)gq_n * 4 + 15) & ~15ul);
+        int32_t* d_v2 = (int32_t*)(d_q2 + qseg);
+        HIP_OR_FAIL(hipMemcpy(d_idx, redo.data(), (size_t)gq_n * 4,
+                              hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
+        launch_gather_rows(d_q2, d_q, (int)row, d_idx, gq_n, nullptr);
+        b2.queries = d_q2;
+        b2.out_vids = d_v2;
+        b2.out_dists = (float*)(d_v2 + (size_t)gq_n * k);
+    }
+    int rc = run_pass(ix, false, c2, b2, out, d_idx, d_vids, d_dists);
+    if (rc != SPTAG_AMD_OK) return rc;
+    /* a query can still overflow at reference capacities only through
+     * visited-table saturation (probe give-up) — that would be a silent
+     * result truncation, so it is an error, not a degradation. */
+    for (int32_t i = 0; i < gq_n; i++) {
+        if (out.oflow[i]) {
+            fprintf(stderr,
+                    "sptag_amd: query overflowed at reference capacities "
+                    "(visited-table saturation)\n");
             return SPTAG_AMD_ERR_INTERNAL;
-        }
-        (void)hipEventRecord(ix->ev1);
-        if (!all_global) {
-            int32_t* d_idx = (int32_t*)ix->d_redo;
-            launch_scatter_rows(d_vids, b2.out_vids, k * 4, d_idx, gq_n, nullptr);
-            launch_scatter_rows(d_dists, b2.out_dists, k * 4, d_idx, gq_n, nullptr);
-        }
-        HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ix->ev0, ix->ev1);
-        ix->last_kernel_ms += ms;
-        HIP_OR_FAIL(hipMemcpy(stats.data(), ix->d_stats,
-                              (size_t)gq_n * sstride * 4,
-                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
-        for (int32_t i = 0; i < gq_n; i++) {
-            ix->last_checked += stats[(size_t)sstride * i];
-            ix->last_popped += stats[(size_t)sstride * i + 1];
-        }
-        /* a query can still overflow at reference capacities only through
-         * visited-table saturation (probe give-up) — that would be a silent
-         * result truncation, so it is an error, not a degradation. */
-        std::vector<int32_t> oflow2(gq_n);
-        HIP_OR_FAIL(hipMemcpy(oflow2.data(), ix->d_oflow, (size_t)gq_n * 4,
-                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
-        for (int32_t i = 0; i < gq_n; i++) {
-            if (oflow2[i]) {
-                fprintf(stderr,
-                        "sptag_amd: query overflowed at reference capacities "
-                        "(visited-table saturation)\n");
-                return SPTAG_AMD_ERR_INTERNAL;
-            }
         }
     }
     return SPTAG_AMD_OK;
@@ -665,28 +721,21 @@ int sptag_amd_search_batch(SptagAmdIndex* ix, const void* queries, int32_t nq,
     std::lock_guard<std::mutex> g(ix->lock);
     HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
 
-    size_t qbytes = (size_t)nq * ix->dim * ix->esz();
-    void* d_q = nullptr;
-    int32_t* d_vids = nullptr;
-    float* d_dists = nullptr;
-    rc = SPTAG_AMD_ERR_NOGPU;
-    do {
-        if (hipMalloc(&d_q, qbytes) != hipSuccess) { rc = SPTAG_AMD_ERR_OOM; break; }
-        if (hipMalloc(&d_vids, (size_t)nq * k * 4) != hipSuccess) { rc = SPTAG_AMD_ERR_OOM; break; }
-        if (hipMalloc(&d_dists, (size_t)nq * k * 4) != hipSuccess) { rc = SPTAG_AMD_ERR_OOM; break; }
-        if (hipMemcpy(d_q, queries, qbytes, hipMemcpyHostToDevice) != hipSuccess) break;
-        rc = search_device_core(ix, d_q, nq, k, max_check, d_vids, d_dists);
-        if (rc != SPTAG_AMD_OK) break;
-        if (hipMemcpy(out_vids, d_vids, (size_t)nq * k * 4, hipMemcpyDeviceToHost)
-            != hipSuccess) { rc = SPTAG_AMD_ERR_NOGPU; break; }
-        if (hipMemcpy(out_dists, d_dists, (size_t)nq * k * 4, hipMemcpyDeviceToHost)
-            != hipSuccess) { rc = SPTAG_AMD_ERR_NOGPU; break; }
-        rc = SPTAG_AMD_OK;
-    } while (0);
-    if (d_q) (void)hipFree(d_q);
-    if (d_vids) (void)hipFree(d_vids);
-    if (d_dists) (void)hipFree(d_dists);
-    return rc;
+    const size_t obytes = (size_t)nq * k * 4;
+    DevBuf d_q, d_vids, d_dists;
+    HIP_OR_FAIL(d_q.alloc((size_t)nq * ix->dim * ix->esz()), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_vids.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_dists.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(hipMemcpy(d_q.as(), queries, (size_t)nq * ix->dim * ix->esz(),
+                          hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
+    rc = search_device_core(ix, d_q.as(), nq, k, max_check, d_vids.as<int32_t>(),
+                            d_dists.as<float>());
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(hipMemcpy(out_vids, d_vids.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_dists, d_dists.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
 }
 
 void sptag_amd_last_stats(SptagAmdIndex* ix, double* kernel_ms,
@@ -699,19 +748,12 @@ void sptag_amd_last_stats(SptagAmdIndex* ix, double* kernel_ms,
 }
 
 struct SptagAmdIterBatch {
-    SptagAmdIndex* ix;
-    int32_t nq, max_check, vcap, ng_cap, spt_cap, dpq_alloc;
-    void* d_q = nullptr;
-    void* d_ng = nullptr;
-    void* d_spt = nullptr;
-    float* d_dpq = nullptr;
-    int32_t* d_visited = nullptr;
-    IterState* d_state = nullptr;
-    int32_t* d_ov = nullptr;
-    float* d_od = nullptr;
-    int32_t* d_oc = nullptr;
-    int32_t* d_or = nullptr;
-    int32_t out_cap = 0;
+    SptagAmdIndex* ix = nullptr;
+    int32_t nq = 0, max_check = 0, vcap = 0, ng_cap = 0, spt_cap = 0, dpq_alloc = 0;
+    /* queries and persistent traversal state */
+    DevBuf d_q, d_ng, d_spt, d_dpq, d_visited, d_state;
+    /* per-call outputs; d_ov/d_od grow with the largest batch asked for */
+    DevBuf d_ov, d_od, d_oc, d_or;
 };
 
 SptagAmdIterBatch* sptag_amd_iter_create(SptagAmdIndex* ix, const void* queries,
@@ -730,7 +772,7 @@ SptagAmdIterBatch* sptag_amd_iter_create(SptagAmdIndex* ix, const void* queries,
         return nullptr;
     }
     if (max_check <= 0) max_check = ix->default_maxcheck;
-    auto* it = new SptagAmdIterBatch();
+    std::unique_ptr<SptagAmdIterBatch> it(new SptagAmdIterBatch());
     it->ix = ix;
     it->nq = nq;
     it->max_check = max_check;
@@ -738,44 +780,27 @@ SptagAmdIterBatch* sptag_amd_iter_create(SptagAmdIndex* ix, const void* queries,
     it->spt_cap = max_check * 10;
     it->dpq_alloc = std::max(max_check / 16, (int)MAX_K);
     it->vcap = (int32_t)next_pow2((uint32_t)std::max(4096, max_check * 4));
-    size_t qb = (size_t)nq * ix->dim * ix->esz();
-    bool ok = hipMalloc(&it->d_q, qb) == hipSuccess &&
-        hipMemcpy(it->d_q, queries, qb, hipMemcpyHostToDevice) == hipSuccess &&
-        hipMalloc(&it->d_ng, (size_t)nq * (it->ng_cap + 1) * 8) == hipSuccess &&
-        hipMalloc(&it->d_spt, (size_t)nq * (it->spt_cap + 1) * 8) == hipSuccess &&
-        hipMalloc(&it->d_dpq, (size_t)nq * (it->dpq_alloc + 1) * 4) == hipSuccess &&
-        hipMalloc(&it->d_visited, (size_t)nq * it->vcap * 4) == hipSuccess &&
-        hipMemset(it->d_visited, 0, (size_t)nq * it->vcap * 4) == hipSuccess &&
-        hipMalloc(&it->d_state, (size_t)nq * sizeof(IterState)) == hipSuccess &&
-        hipMalloc(&it->d_oc, (size_t)nq * 4) == hipSuccess &&
-        hipMalloc(&it->d_or, (size_t)nq * 4) == hipSuccess;
-    if (ok) {
-        std::vector<IterState> init(nq);
-        for (auto& st : init) { st = IterState{}; st.first = 1; }
-        ok = hipMemcpy(it->d_state, init.data(), (size_t)nq * sizeof(IterState),
-                       hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) {
-        sptag_amd_iter_free(it);
+    std::vector<IterState> init(nq);
+    for (auto& st : init) { st = IterState{}; st.first = 1; }
+    const size_t vbytes = (size_t)nq * it->vcap * 4;
+    if (dev_upload(it->d_q, queries, (size_t)nq * ix->dim * ix->esz()) != SPTAG_AMD_OK)
         return nullptr;
-    }
-    return it;
+    HIP_OR_FAIL(it->d_ng.alloc((size_t)nq * (it->ng_cap + 1) * 8), nullptr);
+    HIP_OR_FAIL(it->d_spt.alloc((size_t)nq * (it->spt_cap + 1) * 8), nullptr);
+    HIP_OR_FAIL(it->d_dpq.alloc((size_t)nq * (it->dpq_alloc + 1) * 4), nullptr);
+    HIP_OR_FAIL(it->d_visited.alloc(vbytes), nullptr);
+    HIP_OR_FAIL(hipMemset(it->d_visited.as(), 0, vbytes), nullptr);
+    HIP_OR_FAIL(it->d_oc.alloc((size_t)nq * 4), nullptr);
+    HIP_OR_FAIL(it->d_or.alloc((size_t)nq * 4), nullptr);
+    if (dev_upload(it->d_state, init.data(), (size_t)nq * sizeof(IterState)) !=
+        SPTAG_AMD_OK)
+        return nullptr;
+    return it.release();
 }
 
 void sptag_amd_iter_free(SptagAmdIterBatch* it)
 {
-    if (!it) return;
-    if (it->d_q) (void)hipFree(it->d_q);
-    if (it->d_ng) (void)hipFree(it->d_ng);
-    if (it->d_spt) (void)hipFree(it->d_spt);
-    if (it->d_dpq) (void)hipFree(it->d_dpq);
-    if (it->d_visited) (void)hipFree(it->d_visited);
-    if (it->d_state) (void)hipFree(it->d_state);
-    if (it->d_ov) (void)hipFree(it->d_ov);
-    if (it->d_od) (void)hipFree(it->d_od);
-    if (it->d_oc) (void)hipFree(it->d_oc);
-    if (it->d_or) (void)hipFree(it->d_or);
-    delete it;
+    if (it) delete it;
 }
 
 int sptag_amd_iter_next(SptagAmdIterBatch* it, int32_t batch,
@@ -786,57 +811,40 @@ int sptag_amd_iter_next(SptagAmdIterBatch* it, int32_t batch,
     SptagAmdIndex* ix = it->ix;
     std::lock_guard<std::mutex> g(ix->lock);
     HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
-    if (batch > it->out_cap) {
-        if (it->d_ov) (void)hipFree(it->d_ov);
-        if (it->d_od) (void)hipFree(it->d_od);
-        it->d_ov = nullptr; it->d_od = nullptr; it->out_cap = 0;
-        if (hipMalloc(&it->d_ov, (size_t)it->nq * batch * 4) != hipSuccess ||
-            hipMalloc(&it->d_od, (size_t)it->nq * batch * 4) != hipSuccess)
-            return SPTAG_AMD_ERR_OOM;
-        it->out_cap = batch;
-    }
-    SearchCfg cfg;
-    cfg.nq = it->nq;
-    cfg.k = batch;
-    cfg.max_check = it->max_check;
-    cfg.init_pivots = ix->init_pivots;
-    cfg.other_pivots = ix->other_pivots;
-    cfg.nobetter_threshold = ix->nobetter_threshold;
-    cfg.search_dup = 1;
-    cfg.search_deleted = 0;
-    cfg.dpq_cap = std::max(it->max_check / 16, batch);  /* ResetResult cap */
+    const size_t obytes = (size_t)it->nq * batch * 4;
+    HIP_OR_FAIL(it->d_ov.ensure(obytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(it->d_od.ensure(obytes), SPTAG_AMD_ERR_OOM);
+    /* dpq_cap comes out as the ResetResult cap, max(max_check/16, batch) */
+    SearchCfg cfg = base_cfg(ix, it->nq, batch, it->max_check, false);
     cfg.vcap = it->vcap;
     cfg.ng_cap = it->ng_cap;
     cfg.spt_cap = it->spt_cap;
-    cfg.spec_flags = 0;
-    if (const char* e = getenv("SPTAG_AMD_SPEC")) cfg.spec_flags = atoi(e);
-    cfg.prof = 0;
 
     IterBufs ib;
-    ib.queries = it->d_q;
-    ib.gheap_ng = it->d_ng;
-    ib.gheap_spt = it->d_spt;
-    ib.dpq = it->d_dpq;
-    ib.visited = it->d_visited;
-    ib.state = it->d_state;
-    ib.out_vids = it->d_ov;
-    ib.out_dists = it->d_od;
-    ib.out_counts = it->d_oc;
-    ib.out_relaxed = it->d_or;
+    ib.queries = it->d_q.as();
+    ib.gheap_ng = it->d_ng.as();
+    ib.gheap_spt = it->d_spt.as();
+    ib.dpq = it->d_dpq.as<float>();
+    ib.visited = it->d_visited.as<int32_t>();
+    ib.state = it->d_state.as<IterState>();
+    ib.out_vids = it->d_ov.as<int32_t>();
+    ib.out_dists = it->d_od.as<float>();
+    ib.out_counts = it->d_oc.as<int32_t>();
+    ib.out_relaxed = it->d_or.as<int32_t>();
     int err = launch_bkt_iter(ix->vt, ix->dm, ix->dev(), cfg, ib, batch, nullptr);
     if (err != 0) {
         fprintf(stderr, "sptag_amd: iter launch failed %d\n", err);
         return SPTAG_AMD_ERR_INTERNAL;
     }
     HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_vids, it->d_ov, (size_t)it->nq * batch * 4,
-                          hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_dists, it->d_od, (size_t)it->nq * batch * 4,
-                          hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_counts, it->d_oc, (size_t)it->nq * 4,
+    HIP_OR_FAIL(hipMemcpy(out_vids, ib.out_vids, obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_dists, ib.out_dists, obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_counts, ib.out_counts, (size_t)it->nq * 4,
                           hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
     if (out_relaxed)
-        HIP_OR_FAIL(hipMemcpy(out_relaxed, it->d_or, (size_t)it->nq * 4,
+        HIP_OR_FAIL(hipMemcpy(out_relaxed, ib.out_relaxed, (size_t)it->nq * 4,
                               hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
     return SPTAG_AMD_OK;
 }
@@ -849,28 +857,22 @@ int sptag_amd_truth(SptagAmdIndex* ix, const void* queries, int32_t nq,
     std::lock_guard<std::mutex> g(ix->lock);
     HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
 
-    size_t qbytes = (size_t)nq * ix->dim * ix->esz();
-    void* d_q = nullptr;
-    int32_t* d_v = nullptr;
-    float* d_d = nullptr;
-    HIP_OR_FAIL(hipMalloc(&d_q, qbytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMalloc(&d_v, (size_t)nq * k * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMalloc(&d_d, (size_t)nq * k * 4), SPTAG_AMD_ERR_OOM);
-    int rc = SPTAG_AMD_ERR_NOGPU;
-    if (hipMemcpy(d_q, queries, qbytes, hipMemcpyHostToDevice) == hipSuccess) {
-        int err = launch_truth(ix->vt, ix->dm, ix->dev(), d_q, nq, k, d_v, d_d,
-                               nullptr);
-        if (err == 0 && hipDeviceSynchronize() == hipSuccess &&
-            hipMemcpy(out_vids, d_v, (size_t)nq * k * 4,
-                      hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(out_dists, d_d, (size_t)nq * k * 4,
-                      hipMemcpyDeviceToHost) == hipSuccess)
-            rc = SPTAG_AMD_OK;
-    }
-    (void)hipFree(d_q);
-    (void)hipFree(d_v);
-    (void)hipFree(d_d);
-    return rc;
+    const size_t qbytes = (size_t)nq * ix->dim * ix->esz(), obytes = (size_t)nq * k * 4;
+    DevBuf d_q, d_v, d_d;
+    HIP_OR_FAIL(d_q.alloc(qbytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_v.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_d.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(hipMemcpy(d_q.as(), queries, qbytes, hipMemcpyHostToDevice),
+                SPTAG_AMD_ERR_NOGPU);
+    if (launch_truth(ix->vt, ix->dm, ix->dev(), d_q.as(), nq, k, d_v.as<int32_t>(),
+                     d_d.as<float>(), nullptr) != 0)
+        return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_vids, d_v.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_dists, d_d.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
 }
 
 /* Host-side distance restatements for the add path's edge arithmetic
@@ -1025,25 +1027,18 @@ int sptag_amd_add(SptagAmdIndex* ix, const void* vectors, int32_t nadd,
         }
     }
 
-    /* device: re-allocate vectors+graph at the new size */
-    void* nv = nullptr;
-    int32_t* ng = nullptr;
-    HIP_OR_FAIL(hipMalloc(&nv, ix->h_vectors.size()), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(nv, ix->h_vectors.data(), ix->h_vectors.size(),
-                          hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMalloc(&ng, ix->h_graph.size() * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(ng, ix->h_graph.data(), ix->h_graph.size() * 4,
-                          hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-    (void)hipFree(ix->d_vectors);
-    (void)hipFree(ix->d_graph);
-    ix->d_vectors = nv;
-    ix->d_graph = ng;
+    /* device: re-allocate vectors+graph at the new size; the handle keeps
+     * its old arrays until both uploads have succeeded */
+    DevBuf nv, ng;
+    int rc = dev_upload(nv, ix->h_vectors.data(), ix->h_vectors.size());
+    if (rc == SPTAG_AMD_OK)
+        rc = dev_upload(ng, ix->h_graph.data(), ix->h_graph.size() * 4);
+    if (rc != SPTAG_AMD_OK) return rc;
+    ix->d_vectors = std::move(nv);
+    ix->d_graph = std::move(ng);
     if (ix->has_deleted) {
-        (void)hipFree(ix->d_deleted);
-        HIP_OR_FAIL(hipMalloc(&ix->d_deleted, ix->h_deleted.size()), SPTAG_AMD_ERR_OOM);
-        HIP_OR_FAIL(hipMemcpy(ix->d_deleted, ix->h_deleted.data(),
-                              ix->h_deleted.size(), hipMemcpyHostToDevice),
-                    SPTAG_AMD_ERR_NOGPU);
+        rc = dev_upload(ix->d_deleted, ix->h_deleted.data(), ix->h_deleted.size());
+        if (rc != SPTAG_AMD_OK) return rc;
     }
 
     /* per new node: RefineNode (search CEF+1 at MaxCheckForRefineGraph with
@@ -1053,37 +1048,27 @@ int sptag_amd_add(SptagAmdIndex* ix, const void* vectors, int32_t nadd,
     const int k = 500 + 1;   /* AddCEF default (ParameterDefinitionList) */
     std::vector<int32_t> rv(k);
     std::vector<float> rd(k);
-    int32_t* d_v = nullptr;
-    float* d_d = nullptr;
-    void* d_q = nullptr;
-    /* staging for the batched changed-row upload: one H2D + one scatter
-     * per added node instead of one 128 B hipMemcpy per touched edge (the
-     * round-1 form did up to ~500 tiny copies per add). The SEARCH stays
-     * sequential per node — reference AddIndex semantics (BKTIndex.cpp:
-     * 966-969: each refine sees every previously added node's edges). */
-    int32_t* d_rows = nullptr;     /* staged row payloads */
-    int32_t* d_rowidx = nullptr;   /* their row ids */
-    HIP_OR_FAIL(hipMalloc(&d_v, (size_t)k * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMalloc(&d_d, (size_t)k * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMalloc(&d_q, (size_t)ix->dim * esz), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMalloc(&d_rows, (size_t)(k + 1) * ix->deg * 4),
-                SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMalloc(&d_rowidx, (size_t)(k + 1) * 4), SPTAG_AMD_ERR_OOM);
+    /* d_rows/d_rowidx stage the batched changed-row upload: one H2D + one
+     * scatter per added node instead of one 128 B hipMemcpy per touched
+     * edge (the round-1 form did up to ~500 tiny copies per add). */
+    DevBuf d_v, d_d, d_q, d_rows, d_rowidx;
+    HIP_OR_FAIL(d_v.alloc((size_t)k * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_d.alloc((size_t)k * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_q.alloc((size_t)ix->dim * esz), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_rows.alloc((size_t)(k + 1) * ix->deg * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_rowidx.alloc((size_t)(k + 1) * 4), SPTAG_AMD_ERR_OOM);
     std::vector<int32_t> hrows((size_t)(k + 1) * ix->deg);
     std::vector<int32_t> hidx(k + 1);
-    int rc = SPTAG_AMD_OK;
-    for (int32_t node = begin; node < end && rc == SPTAG_AMD_OK; node++) {
-        HIP_OR_FAIL(hipMemcpy(d_q, hvec(ix, node), (size_t)ix->dim * esz,
+    for (int32_t node = begin; node < end; node++) {
+        HIP_OR_FAIL(hipMemcpy(d_q.as(), hvec(ix, node), (size_t)ix->dim * esz,
                               hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-        ix->refine_mode = true;
-        rc = search_device_core(ix, d_q, 1, k, 8192 /*MaxCheckForRefineGraph*/,
-                                d_v, d_d);
-        ix->refine_mode = false;
-        if (rc != SPTAG_AMD_OK) break;
-        HIP_OR_FAIL(hipMemcpy(rv.data(), d_v, (size_t)k * 4, hipMemcpyDeviceToHost),
-                    SPTAG_AMD_ERR_NOGPU);
-        HIP_OR_FAIL(hipMemcpy(rd.data(), d_d, (size_t)k * 4, hipMemcpyDeviceToHost),
-                    SPTAG_AMD_ERR_NOGPU);
+        rc = search_device_core(ix, d_q.as(), 1, k, 8192 /*MaxCheckForRefineGraph*/,
+                                d_v.as<int32_t>(), d_d.as<float>(), true);
+        if (rc != SPTAG_AMD_OK) return rc;
+        HIP_OR_FAIL(hipMemcpy(rv.data(), d_v.as(), (size_t)k * 4,
+                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
+        HIP_OR_FAIL(hipMemcpy(rd.data(), d_d.as(), (size_t)k * 4,
+                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
         host_rebuild_neighbors(ix, node, rv.data(), rd.data(), k);
         int nrows = 0;
         hidx[nrows++] = node;
@@ -1101,21 +1086,15 @@ int sptag_amd_add(SptagAmdIndex* ix, const void* vectors, int32_t nadd,
             memcpy(&hrows[(size_t)j * ix->deg],
                    ix->h_graph.data() + (size_t)hidx[j] * ix->deg,
                    (size_t)ix->deg * 4);
-        HIP_OR_FAIL(hipMemcpy(d_rows, hrows.data(),
-                              (size_t)nrows * ix->deg * 4,
+        HIP_OR_FAIL(hipMemcpy(d_rows.as(), hrows.data(), (size_t)nrows * ix->deg * 4,
                               hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-        HIP_OR_FAIL(hipMemcpy(d_rowidx, hidx.data(), (size_t)nrows * 4,
+        HIP_OR_FAIL(hipMemcpy(d_rowidx.as(), hidx.data(), (size_t)nrows * 4,
                               hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-        launch_scatter_rows(ix->d_graph, d_rows, ix->deg * 4, d_rowidx, nrows,
-                            nullptr);
+        launch_scatter_rows(ix->d_graph.as(), d_rows.as(), ix->deg * 4,
+                            d_rowidx.as<int32_t>(), nrows, nullptr);
         HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
     }
-    (void)hipFree(d_v);
-    (void)hipFree(d_d);
-    (void)hipFree(d_q);
-    (void)hipFree(d_rows);
-    (void)hipFree(d_rowidx);
-    return rc;
+    return SPTAG_AMD_OK;
 }
 
 int sptag_amd_delete_by_vector(SptagAmdIndex* ix, const void* vectors,
@@ -1158,10 +1137,8 @@ int sptag_amd_delete(SptagAmdIndex* ix, const int32_t* vids, int32_t n)
     ix->has_deleted = ix->deleted_count > 0;
     if (sptag_amd_gpu_available() && ix->d_vectors) {
         HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
-        if (!ix->d_deleted)
-            HIP_OR_FAIL(hipMalloc(&ix->d_deleted, ix->h_deleted.size()),
-                        SPTAG_AMD_ERR_OOM);
-        HIP_OR_FAIL(hipMemcpy(ix->d_deleted, ix->h_deleted.data(),
+        HIP_OR_FAIL(ix->d_deleted.ensure(ix->h_deleted.size()), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(hipMemcpy(ix->d_deleted.as(), ix->h_deleted.data(),
                               ix->h_deleted.size(), hipMemcpyHostToDevice),
                     SPTAG_AMD_ERR_NOGPU);
     }
@@ -1179,37 +1156,26 @@ int sptag_amd_save_index(SptagAmdIndex* ix, const char* folder)
     std::string dir(folder);
     if (!dir.empty() && dir.back() != '/') dir += '/';
 
-    auto wfile = [&](const std::string& name, const void* hdr, size_t hdrsz,
-                     const void* body, size_t bodysz) -> bool {
-        FILE* f = fopen((dir + name).c_str(), "wb");
-        if (!f) return false;
-        bool ok = fwrite(hdr, 1, hdrsz, f) == hdrsz &&
-                  (bodysz == 0 || fwrite(body, 1, bodysz, f) == bodysz);
-        fclose(f);
-        return ok;
-    };
-
     int32_t vh[2] = {ix->n, ix->dim};
-    if (!wfile("vectors.bin", vh, 8, ix->h_vectors.data(), ix->h_vectors.size()))
+    if (!write_file(dir + "vectors.bin",
+                    {{vh, 8}, {ix->h_vectors.data(), ix->h_vectors.size()}}))
         return SPTAG_AMD_ERR_IO;
-    {
-        FILE* f = fopen((dir + "tree.bin").c_str(), "wb");
-        if (!f) return SPTAG_AMD_ERR_IO;
-        fwrite(&ix->ntrees, 4, 1, f);
-        fwrite(ix->h_tree_start.data(), 4, ix->ntrees, f);
-        fwrite(&ix->n_tree_nodes, 4, 1, f);
-        fwrite(ix->h_tree.data(), ix->algo == ALGO_KDT ? 16 : 12,
-               ix->n_tree_nodes, f);
-        fclose(f);
-    }
+    const size_t node_bytes = ix->algo == ALGO_KDT ? 16 : 12;
+    if (!write_file(dir + "tree.bin",
+                    {{&ix->ntrees, 4},
+                     {ix->h_tree_start.data(), (size_t)ix->ntrees * 4},
+                     {&ix->n_tree_nodes, 4},
+                     {ix->h_tree.data(), (size_t)ix->n_tree_nodes * node_bytes}}))
+        return SPTAG_AMD_ERR_IO;
     int32_t gh[2] = {ix->n, ix->deg};
-    if (!wfile("graph.bin", gh, 8, ix->h_graph.data(), ix->h_graph.size() * 4))
+    if (!write_file(dir + "graph.bin",
+                    {{gh, 8}, {ix->h_graph.data(), ix->h_graph.size() * 4}}))
         return SPTAG_AMD_ERR_IO;
     {
         std::vector<uint8_t> del = ix->h_deleted;
         if (del.empty()) del.assign((size_t)ix->n, 0);
         int32_t dh[3] = {(int32_t)ix->deleted_count, ix->n, 1};
-        if (!wfile("deletes.bin", dh, 12, del.data(), del.size()))
+        if (!write_file(dir + "deletes.bin", {{dh, 12}, {del.data(), del.size()}}))
             return SPTAG_AMD_ERR_IO;
     }
     {
@@ -1281,6 +1247,7 @@ void sptag_amd_set_search_params(SptagAmdIndex* ix, int32_t init_pivots,
                                  int32_t default_maxcheck)
 {
     if (!ix) return;
+    std::lock_guard<std::mutex> g(ix->lock);   /* a search may be in flight */
     if (init_pivots > 0) ix->init_pivots = init_pivots;
     if (other_pivots > 0) ix->other_pivots = other_pivots;
     if (nobetter_threshold > 0) ix->nobetter_threshold = nobetter_threshold;

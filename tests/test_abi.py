@@ -207,3 +207,108 @@ def test_load_tolerant_ini(tmp_path):
     assert ix.n == g["meta"]["n"]
     assert ix.distmethod == sptag_amd.DM_L2
     assert ix.default_maxcheck == 8192
+
+
+def _tree_header_bytes(path):
+    ntrees = int(np.fromfile(path, dtype=np.int32, count=1)[0])
+    return 4 + 4 * ntrees + 4
+
+
+@pytest.mark.parametrize("name", ["f32_l2_n10k_d32", "kdt_f32_l2_n10k_d32"])
+def test_truncated_folder_fails_to_load(tmp_path, name):
+    """A short or empty vectors/tree/graph file is a failed load (null
+    handle, process alive), never a read past the file's bytes."""
+    import shutil
+    lib = sptag_amd.load_library()
+    g = load_golden(name)
+    dst = tmp_path / "index"
+    shutil.copytree(g["index"], dst)
+    header = {"vectors.bin": 8, "graph.bin": 8,
+              "tree.bin": _tree_header_bytes(dst / "tree.bin")}
+    for fname, hdr in header.items():
+        whole = (dst / fname).read_bytes()
+        assert len(whole) > hdr
+        for size in (0, 4, hdr, len(whole) - 1):
+            (dst / fname).write_bytes(whole[:size])
+            h = lib.sptag_amd_load_index(str(dst).encode(), 0)
+            assert h is None, f"{fname} cut to {size} bytes still loaded"
+        (dst / fname).write_bytes(whole)
+    ix = AnnIndex.Load(str(dst))   # the restored copy still loads
+    assert ix.n == g["meta"]["n"] and ix.dim == g["meta"]["dim"]
+
+
+MAX_DIM, MAX_DEG = 4096, 64   # sptag_amd/csrc/common.h
+
+
+def _create(algo, n=4, dim=4, degree=2, ntrees=1, dtype=np.float32,
+            deleted=None):
+    """Call sptag_amd_create_index / _kdt on tiny arrays sized for the
+    arguments given; returns the raw handle (None when refused)."""
+    import ctypes
+    lib = sptag_amd.load_library()
+    rows = max(n, 1)
+    vectors = np.zeros((rows, dim), dtype=dtype)
+    tree_start = np.zeros(max(ntrees, 1), dtype=np.int32)
+    nodes = np.zeros((2, 4 if algo == "kdt" else 3), dtype=np.int32)
+    graph = np.full((rows, degree), -1, dtype=np.int32)
+    fn = (lib.sptag_amd_create_index_kdt if algo == "kdt"
+          else lib.sptag_amd_create_index)
+    vt = sptag_amd.VT_FLOAT if dtype == np.float32 else sptag_amd.VT_INT8
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    return fn(n, dim, vt, sptag_amd.DM_L2, p(vectors), ntrees, p(tree_start),
+              len(nodes), p(nodes), degree, p(graph),
+              p(deleted) if deleted is not None else None, 0)
+
+
+@pytest.mark.parametrize("algo", ["bkt", "kdt"])
+def test_create_validation(algo):
+    """Both create entry points refuse the same bad arguments and build
+    the same handle from good ones."""
+    assert _create(algo, dim=MAX_DIM + 1) is None
+    assert _create(algo, degree=MAX_DEG + 1) is None
+    assert _create(algo, n=0) is None
+    assert _create(algo, ntrees=0) is None
+    # smallest dim at which dim*254*254 >= 2^24: int8 distances stop
+    # being exact integers in float
+    assert 260 * 254 * 254 < 2 ** 24 <= 261 * 254 * 254
+    assert _create(algo, dim=261, dtype=np.int8) is None
+    h = _create(algo, dim=260, dtype=np.int8)
+    assert h is not None
+    sptag_amd.load_library().sptag_amd_free_index(h)
+
+    deleted = np.array([0, 1, 0, 1], dtype=np.uint8)
+    ix = AnnIndex(_create(algo, deleted=deleted))
+    assert (ix.n, ix.dim, ix.degree) == (4, 4, 2)
+    assert ix.algo == (1 if algo == "kdt" else 0)
+    assert ix.valuetype == sptag_amd.VT_FLOAT
+    assert ix.deleted_count == 2
+
+
+@pytest.mark.parametrize("name", ["f32_l2_n10k_d32", "kdt_f32_l2_n10k_d32"])
+def test_save_is_stable(tmp_path, name):
+    """load -> save A -> load A -> save B: all five files byte-identical,
+    and search parameters set before the first save reach the handle
+    loaded from B (read back through the getter and through a third save
+    of that handle)."""
+    files = ["vectors.bin", "tree.bin", "graph.bin", "deletes.bin",
+             "indexloader.ini"]
+    g = load_golden(name)
+    ix = AnnIndex.Load(g["index"])
+    ix.SetSearchParams(init_pivots=37, other_pivots=5, nobetter_threshold=7,
+                       max_check=4096)
+    a, b, c = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    ix.Save(str(a))
+    AnnIndex.Load(str(a)).Save(str(b))
+    for f in files:
+        assert (a / f).read_bytes() == (b / f).read_bytes(), f
+    ixb = AnnIndex.Load(str(b))
+    assert ixb.default_maxcheck == 4096
+    ixb.Save(str(c))
+    ini = (c / "indexloader.ini").read_text()
+    assert ini == (a / "indexloader.ini").read_text()
+    assert "\nMaxCheck=4096\n" in ini
+    assert "\nNumberOfInitialDynamicPivots=37\n" in ini
+    assert "\nNumberOfOtherDynamicPivots=5\n" in ini
+    if name.startswith("kdt"):   # the BKT template writes its fixed 3
+        assert ("\nThresholdOfNumberOfContinuousNoBetterPropagation=7\n"
+                in ini)
