@@ -69,23 +69,58 @@ struct SearchBufs {
 };
 
 enum { SPT_LDS_TIER_H = 255 };  /* SPT heap LDS tier entries (see kernels) */
+enum { SERIAL_STATE_BYTES = 64 };  /* LDS slot of the kernels' SerialState */
 
-/* LDS bytes needed per workgroup for the LDS-heap variant (and the
- * non-heap part of the global variant). Keep in sync with kernel. */
+#ifdef __HIPCC__
+#define SPTAG_HD __host__ __device__
+#else
+#define SPTAG_HD
+#endif
+
+/* Dynamic-LDS carve-up of the one-wave-per-query kernels: byte offsets of
+ * each region and the total. The kernels take their pointers and the
+ * launchers their LDS size from this one function. */
+struct LdsLayout {
+    uint32_t q, dstage, istage, qrs, dpq, ss, spt_tier, ng, total;
+};
+
+/* nstage: staged candidates (dstage + istage entries each); dpq_cap < 0: no
+ * results queue in LDS; ng_cap == 0: no NG heap in LDS. */
+SPTAG_HD inline LdsLayout lds_layout(int dim, size_t esz, int k, int nstage,
+                                     int dpq_cap, bool spt_tier, int ng_cap)
+{
+    LdsLayout l;
+    uint32_t b = 0;
+    l.q = b;        b += (uint32_t)(((size_t)dim * esz + 15) & ~15ul);  /* query vector */
+    l.dstage = b;   b += (uint32_t)nstage * 4;             /* staged dists */
+    l.istage = b;   b += (uint32_t)nstage * 4;             /* staged ids */
+    l.qrs = b;      b += (uint32_t)k * 8;                  /* result set */
+    l.dpq = b;      if (dpq_cap >= 0) b += ((uint32_t)dpq_cap + 1) * 4;  /* DistPriorityQueue */
+    l.ss = b;       b += SERIAL_STATE_BYTES;               /* scalar slots, padding */
+    l.spt_tier = b; if (spt_tier) b += ((uint32_t)SPT_LDS_TIER_H + 1) * 8;
+    l.ng = b;       if (ng_cap > 0) b += ((uint32_t)ng_cap + 1) * 8;  /* SPT heap tail is global */
+    l.total = b;
+    return l;
+}
+
+/* batched BKT/KDT search; the KDT kernel reserves the results queue too */
 inline size_t lds_bytes(int dim, size_t esz, const SearchCfg& c, bool heaps_in_lds)
 {
-    size_t b = 0;
-    b += ((size_t)dim * esz + 15) & ~15ul;            /* query vector */
-    b += (MAX_DEG) * 4;                               /* staged dists */
-    b += (MAX_DEG) * 4;                               /* staged child centers */
-    b += ((size_t)c.k) * 8;                           /* result set */
-    b += ((size_t)c.dpq_cap + 1) * 4;                 /* DistPriorityQueue */
-    b += 64;                                          /* scalar slots, padding */
-    b += ((size_t)SPT_LDS_TIER_H + 1) * 8;            /* SPT heap LDS tier */
-    if (heaps_in_lds) {
-        b += ((size_t)c.ng_cap + 1) * 8;   /* SPT heap tail is global */
-    }
-    return b;
+    return lds_layout(dim, esz, c.k, MAX_DEG, c.dpq_cap, true,
+                      heaps_in_lds ? c.ng_cap : 0).total;
+}
+
+/* iterative search: results queue and both heaps persist in global memory */
+SPTAG_HD inline LdsLayout iter_lds_layout(int dim, size_t esz, int batch)
+{
+    return lds_layout(dim, esz, batch, MAX_DEG, -1, false, 0);
+}
+
+/* brute-force truth: query and result set only; its four staged distances
+ * sit in the scalar slot */
+SPTAG_HD inline LdsLayout truth_lds_layout(int dim, size_t esz, int k)
+{
+    return lds_layout(dim, esz, k, 0, -1, false, 0);
 }
 
 /* persistent per-iterator device state (iterative search) */

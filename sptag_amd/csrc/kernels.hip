@@ -30,6 +30,8 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace sptag_amd {
@@ -246,6 +248,13 @@ DEV int visited_test_insert(int32_t* tab, uint32_t mask, int32_t idx, int* oflow
  * distances — one candidate per 16-lane group, reference order
  * ------------------------------------------------------------------ */
 
+/* the fused per-element step of both metrics */
+template <int DM>
+DEV float acc(float x, float y, float a)
+{
+    return (DM == DM_L2) ? fmaf(x - y, x - y, a) : fmaf(x, y, a);
+}
+
 /* float: the AVX512 chunk/fold order of DistanceUtils.cpp:650 (L2) /
  * the cosine analog, with fused lane accumulate (fmaf) as compiled in
  * the reference build (see oracle/sptag_oracle.c header). Result valid
@@ -254,23 +263,50 @@ DEV int visited_test_insert(int32_t* tab, uint32_t mask, int32_t idx, int* oflow
  * The fixed-dim form fully unrolls the 16-element chunk loop so the
  * per-candidate global loads all issue before the fma chain waits on
  * them (the rolled loop costs one memory latency PER CHUNK — 8x the
- * stalls at d=128). Dims must be multiples of 16. */
+ * stalls at d=128). Dims must be multiples of 16.
+ *
+ * It is split into load and reduce for software-pipelining candidate
+ * rounds (loads of round r+1 issue while round r reduces). Only the
+ * candidate's elements are register-resident: the query side is re-read
+ * from LDS in the reduce (cheap ds_reads), keeping the pipeline's
+ * register cost at C floats per fragment. */
+template <int DM, int DFIX>
+struct FragF32 {
+    static constexpr int C = DFIX / 16;
+    float y[C];
+    DEV void load(const float* __restrict__ v)
+    {
+        const int g = threadIdx.x & 15;
+#pragma unroll
+        for (int c = 0; c < C; c++) y[c] = v[c * 16 + g];
+    }
+    /* xat(c) yields this lane's query element of chunk c */
+    template <typename XAt>
+    DEV float reduce_with(XAt xat) const
+    {
+        float a = 0.0f;
+#pragma unroll
+        for (int c = 0; c < C; c++) a = acc<DM>(xat(c), y[c], a);
+        a = a + __shfl_down(a, 8, 16);
+        a = a + __shfl_down(a, 4, 16);
+        float sv = ((__shfl(a, 0, 16) + __shfl(a, 1, 16)) + __shfl(a, 2, 16)) +
+                   __shfl(a, 3, 16);
+        return (DM == DM_L2) ? sv : 1.0f - sv;
+    }
+    DEV float reduce(const float* __restrict__ q) const
+    {
+        const int g = threadIdx.x & 15;
+        return reduce_with([&](int c) { return q[c * 16 + g]; });
+    }
+};
+
 template <int DM, int DFIX>
 DEV float dist_f32_fix(const float* __restrict__ q, const float* __restrict__ v)
 {
-    const int g = threadIdx.x & 15;
-    constexpr int C = DFIX / 16;
-    float x[C], y[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) { x[c] = q[c * 16 + g]; y[c] = v[c * 16 + g]; }
-    float a = 0.0f;
-#pragma unroll
-    for (int c = 0; c < C; c++)
-        a = (DM == DM_L2) ? fmaf(x[c] - y[c], x[c] - y[c], a) : fmaf(x[c], y[c], a);
-    a = a + __shfl_down(a, 8, 16);
-    a = a + __shfl_down(a, 4, 16);
-    float sv = ((__shfl(a, 0, 16) + __shfl(a, 1, 16)) + __shfl(a, 2, 16)) + __shfl(a, 3, 16);
-    return (DM == DM_L2) ? sv : 1.0f - sv;
+    FragF32<DM, DFIX> x, y;
+    x.load(q);
+    y.load(v);
+    return y.reduce_with([&](int c) { return x.y[c]; });
 }
 
 template <int DM>
@@ -292,30 +328,20 @@ DEV float ref_dist_grp_f32(const float* __restrict__ q,
     float a = 0.0f;
     const int nd16 = (d >> 4) << 4;
     for (int i = 0; i < nd16; i += 16) {
-        float x = q[i + g], y = v[i + g];
-        a = (DM == DM_L2) ? fmaf(x - y, x - y, a) : fmaf(x, y, a);
+        a = acc<DM>(q[i + g], v[i + g], a);
     }
     a = a + __shfl_down(a, 8, 16);           /* a8[g] on lanes g<8 */
     const int nd8 = (d >> 3) << 3;
     for (int i = nd16; i < nd8; i += 8) {
-        if (g < 8) {
-            float x = q[i + g], y = v[i + g];
-            a = (DM == DM_L2) ? fmaf(x - y, x - y, a) : fmaf(x, y, a);
-        }
+        if (g < 8) a = acc<DM>(q[i + g], v[i + g], a);
     }
     a = a + __shfl_down(a, 4, 16);           /* a4[g] on lanes g<4 */
     const int nd4 = (d >> 2) << 2;
     for (int i = nd8; i < nd4; i += 4) {
-        if (g < 4) {
-            float x = q[i + g], y = v[i + g];
-            a = (DM == DM_L2) ? fmaf(x - y, x - y, a) : fmaf(x, y, a);
-        }
+        if (g < 4) a = acc<DM>(q[i + g], v[i + g], a);
     }
     float s = ((__shfl(a, 0, 16) + __shfl(a, 1, 16)) + __shfl(a, 2, 16)) + __shfl(a, 3, 16);
-    for (int i = nd4; i < d; i++) {
-        float x = q[i], y = v[i];
-        s = (DM == DM_L2) ? fmaf(x - y, x - y, s) : fmaf(x, y, s);
-    }
+    for (int i = nd4; i < d; i++) s = acc<DM>(q[i], v[i], s);
     return (DM == DM_L2) ? s : 1.0f - s;
 }
 
@@ -363,60 +389,31 @@ DEV float ref_dist_grp_i8(const int8_t* __restrict__ q,
     return (DM == DM_L2) ? (float)s : (float)(16129 - s);
 }
 
-/* load/compute split of the fixed-dim distance, for software-pipelining
- * candidate rounds (loads of round r+1 issue while round r reduces).
- * Only the candidate's elements are register-resident: the query side is
- * re-read from LDS in the reduce (cheap ds_reads), keeping the pipeline's
- * register cost at C floats per fragment. */
-template <int DM, int DFIX>
-struct FragF32 {
-    static constexpr int C = DFIX / 16;
-    float y[C];
-    DEV void load(const float* __restrict__ v)
-    {
-        const int g = threadIdx.x & 15;
-#pragma unroll
-        for (int c = 0; c < C; c++) y[c] = v[c * 16 + g];
-    }
-    DEV float reduce(const float* __restrict__ q) const
-    {
-        const int g = threadIdx.x & 15;
-        float a = 0.0f;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            float x = q[c * 16 + g];
-            a = (DM == DM_L2) ? fmaf(x - y[c], x - y[c], a) : fmaf(x, y[c], a);
-        }
-        a = a + __shfl_down(a, 8, 16);
-        a = a + __shfl_down(a, 4, 16);
-        float sv = ((__shfl(a, 0, 16) + __shfl(a, 1, 16)) + __shfl(a, 2, 16)) +
-                   __shfl(a, 3, 16);
-        return (DM == DM_L2) ? sv : 1.0f - sv;
-    }
-};
-
 template <typename T, int DM>
-DEV float ref_dist_grp(const T* q, const T* v, int d);
-template <> DEV float ref_dist_grp<float, DM_L2>(const float* q, const float* v, int d)
-{ return ref_dist_grp_f32<DM_L2>(q, v, d); }
-template <> DEV float ref_dist_grp<float, DM_COSINE>(const float* q, const float* v, int d)
-{ return ref_dist_grp_f32<DM_COSINE>(q, v, d); }
-template <> DEV float ref_dist_grp<int8_t, DM_L2>(const int8_t* q, const int8_t* v, int d)
-{ return ref_dist_grp_i8<DM_L2>(q, v, d); }
-template <> DEV float ref_dist_grp<int8_t, DM_COSINE>(const int8_t* q, const int8_t* v, int d)
-{ return ref_dist_grp_i8<DM_COSINE>(q, v, d); }
+DEV float ref_dist_grp(const T* q, const T* v, int d)
+{
+    if constexpr (sizeof(T) == 4)
+        return ref_dist_grp_f32<DM>((const float*)q, (const float*)v, d);
+    else
+        return ref_dist_grp_i8<DM>((const int8_t*)q, (const int8_t*)v, d);
+}
 
 /* ------------------------------------------------------------------ *
  * per-query context
  * ------------------------------------------------------------------ */
 
 struct SerialState {          /* in LDS; lane 0 writes, wave reads after sync */
-    int ng_count, spt_count, dpq_len, checked;
+    int ng_count, spt_count;
+    int dpq_len;                   /* iterative: results-queue length */
+    int checked;
     int oflow, terminate, break_flag, want_tree;
     int tree_checked, no_better;   /* KDT counters */
     float fbcast;                  /* KDT upper-bound broadcast */
     NodeDist popped;
+    int relaxed;                   /* iterative: sticky relaxedMono flag */
 };
+static_assert(sizeof(SerialState) <= SERIAL_STATE_BYTES,
+              "SerialState outgrew its LDS slot");
 
 template <typename T>
 struct QCtx {
@@ -434,6 +431,72 @@ struct QCtx {
     int lane;
 };
 
+/* Query prologue shared by every one-wave-per-query kernel: carve the LDS
+ * regions of `L`, stage query `q`, and let lane 0 start the serial state
+ * from `ss0`, empty the `nres`-entry result set and (on a fresh traversal)
+ * seed both heaps' empty-top sentinels. Ends in the barrier that publishes
+ * all of it. `dpq` overrides the LDS results queue (null = use L.dpq). */
+template <typename T>
+DEV QCtx<T> begin_query(const DevIndex* di, const SearchCfg* cfg, const LdsLayout& L,
+                        const void* queries, int q, int nres, float* dpq,
+                        HeapRef ng, HeapRef spt, int32_t* visited, int32_t vcap,
+                        const SerialState& ss0, bool fresh)
+{
+    extern __shared__ char smem[];
+    const int lane = threadIdx.x;
+    T* qlds = (T*)(smem + L.q);
+    QCtx<T> c{di, cfg, qlds, (float*)(smem + L.dstage), (int32_t*)(smem + L.istage),
+              (QRes*)(smem + L.qrs), dpq ? dpq : (float*)(smem + L.dpq), ng, spt,
+              visited + (size_t)q * vcap, (uint32_t)(vcap - 1),
+              (SerialState*)(smem + L.ss), lane};
+
+    const T* gq = (const T*)queries + (size_t)q * di->dim;
+    for (int i = lane; i < di->dim; i += 64) qlds[i] = gq[i];
+
+    if (lane == 0) {
+        *c.ss = ss0;
+        if (fresh) {
+            hset(ng, 0, NodeDist{-1, MAXDIST});   /* Heap empty-top sentinel */
+            hset(spt, 0, NodeDist{-1, MAXDIST});
+        }
+        for (int i = 0; i < nres; i++) c.qrs[i] = QRes{-1, MAXDIST};
+    }
+    __syncthreads();
+    return c;
+}
+
+/* Result epilogue: lane 0 sorts the result set (SortResult), then the wave
+ * writes query q's k rows. */
+DEV void write_topk(QRes* qrs, int k, int q, int32_t* out_vids, float* out_dists)
+{
+    if (threadIdx.x == 0) qrs_sort(qrs, k);
+    __syncthreads();
+    for (int i = threadIdx.x; i < k; i += 64) {
+        out_vids[(size_t)q * k + i] = qrs[i].vid;
+        out_dists[(size_t)q * k + i] = qrs[i].dist;
+    }
+}
+
+/* Frontier heaps of the batched search kernels. NG: in LDS at its reduced
+ * capacity (LDSHEAP) or in global scratch. SPT (tree) heap: hot top levels
+ * in an LDS tier, tail in global scratch — full reference capacity without
+ * the LDS cost of the whole heap (its all-global round-1 form made the seed
+ * phase 41.5% of kernel cycles). */
+template <bool LDSHEAP>
+DEV void search_heaps(const SearchCfg& cfg, const SearchBufs& bufs, const LdsLayout& L,
+                      int q, HeapRef& ng, HeapRef& spt)
+{
+    extern __shared__ char smem[];
+    ng.cap = cfg.ng_cap;  ng.ref_cap = cfg.max_check * 30;   /* WorkSpace.h:265 */
+    ng.lds = nullptr; ng.lsplit = 0;
+    ng.a = LDSHEAP ? (NodeDist*)(smem + L.ng)
+                   : (NodeDist*)bufs.gheap_ng + (size_t)q * (cfg.ng_cap + 1);
+    spt.cap = cfg.spt_cap; spt.ref_cap = cfg.max_check * 10;
+    spt.a = (NodeDist*)bufs.gheap_spt + (size_t)q * (cfg.spt_cap + 1);
+    spt.lds = (NodeDist*)(smem + L.spt_tier);
+    spt.lsplit = SPT_LDS_TIER;
+}
+
 template <typename T>
 DEV const T* vec_at(const DevIndex& di, int32_t v)
 {
@@ -446,6 +509,19 @@ DEV int not_deleted(const DevIndex& di, int32_t v)
      * dispatch :471-507): deletes ignored when the index has none. */
     if (!di.has_deleted) return 1;
     return di.deleted[v] == 0;
+}
+
+/* Read one byte of every 128B line of vector `vid` (a prefetch the compiler
+ * cannot drop). Returns the sum; the caller sinks it where the loads may
+ * land. */
+template <typename T>
+DEV uint32_t touch_lines(const DevIndex& di, int32_t vid)
+{
+    const char* vp = (const char*)vec_at<T>(di, vid);
+    const int nline = ((int)((unsigned)di.dim * sizeof(T)) + 127) >> 7;
+    uint32_t s = 0;
+    for (int l = 0; l < nline; l++) s += (uint32_t)(uint8_t)vp[(size_t)l << 7];
+    return s;
 }
 
 /* pipelined fixed-dim staging: group g handles candidates g, g+4, ...,
@@ -519,6 +595,37 @@ DEV void spt_warm_parents(QCtx<T>& c, int cnt)
     asm volatile("" :: "v"(wsink));
 }
 
+/* Load the center ids of tree nodes [base, base+cnt) (cnt <= 64) into
+ * istage and stage their distances into dstage. With TOUCH, issue ALL
+ * children's vector lines before the staged distance rounds start: every
+ * one of them is needed (no speculation waste), so the 16 round-pipeline
+ * latencies collapse into one. Seed-phase tree-center gathers were 31% of
+ * kernel cycles. */
+template <typename T, int DM, bool TOUCH>
+DEV void stage_child_dists(QCtx<T>& c, int base, int cnt)
+{
+    if (c.lane < cnt) c.istage[c.lane] = c.di->tree_nodes[(size_t)(base + c.lane) * 3];
+    __syncthreads();
+    uint32_t ts = 0;
+    if (TOUCH && c.lane < cnt) ts = touch_lines<T>(*c.di, c.istage[c.lane]);
+    stage_dists<T, DM>(c, cnt);
+    /* sink after the staging so the touches and the first rounds overlap */
+    if constexpr (TOUCH) asm volatile("" :: "v"(ts));
+}
+
+/* One chunk of a BKT node's children into the SPT heap (lane 0 inserts). */
+template <typename T, int DM>
+DEV void stage_children(QCtx<T>& c, int base, int cnt)
+{
+    stage_child_dists<T, DM, true>(c, base, cnt);
+    spt_warm_parents(c, cnt);
+    if (c.lane == 0)
+        for (int i = 0; i < cnt; i++)
+            ndheap_insert(c.spt, &c.ss->spt_count,
+                          NodeDist{base + i, c.dstage[i]}, &c.ss->oflow);
+    __syncthreads();
+}
+
 /* BKTree.h:772 SearchTrees — wave-cooperative, serial decisions on lane 0. */
 template <typename T, int DM>
 DEV void search_trees_dev(QCtx<T>& c, int limit)
@@ -549,35 +656,8 @@ DEV void search_trees_dev(QCtx<T>& c, int limit)
                     ndheap_insert(c.ng, &c.ss->ng_count, NodeDist{center, bcell.distance}, &c.ss->oflow);
                 }
             }
-            for (int base = cs; base < ce; base += 64) {
-                int cnt = min(64, ce - base);
-                if (c.lane < cnt) c.istage[c.lane] = di.tree_nodes[(size_t)(base + c.lane) * 3];
-                __syncthreads();
-                /* Issue ALL children's vector lines before the staged
-                 * distance rounds start: every one of them is needed (no
-                 * speculation waste), so the 16 round-pipeline latencies
-                 * collapse into one. Seed-phase tree-center gathers were
-                 * 31% of kernel cycles. */
-                uint32_t ts = 0;
-                if (c.lane < cnt) {
-                    const char* vp =
-                        (const char*)vec_at<T>(di, c.istage[c.lane]);
-                    const int nl =
-                        ((int)((unsigned)di.dim * sizeof(T)) + 127) >> 7;
-                    for (int l = 0; l < nl; l++)
-                        ts += (uint32_t)(uint8_t)vp[(size_t)l << 7];
-                }
-                stage_dists<T, DM>(c, cnt);
-                asm volatile("" :: "v"(ts));   /* sink after the staging so
-                                                  the touches and the first
-                                                  rounds overlap */
-                spt_warm_parents(c, cnt);
-                if (c.lane == 0)
-                    for (int i = 0; i < cnt; i++)
-                        ndheap_insert(c.spt, &c.ss->spt_count,
-                                      NodeDist{base + i, c.dstage[i]}, &c.ss->oflow);
-                __syncthreads();
-            }
+            for (int base = cs; base < ce; base += 64)
+                stage_children<T, DM>(c, base, min(64, ce - base));
         }
     }
     __syncthreads();
@@ -601,35 +681,83 @@ DEV void init_search_trees_dev(QCtx<T>& c)
             }
             __syncthreads();
         } else {
-            for (int base = cs; base < ce; base += 64) {
-                int cnt = min(64, ce - base);
-                if (c.lane < cnt) c.istage[c.lane] = di.tree_nodes[(size_t)(base + c.lane) * 3];
-                __syncthreads();
-                /* Issue ALL children's vector lines before the staged
-                 * distance rounds start: every one of them is needed (no
-                 * speculation waste), so the 16 round-pipeline latencies
-                 * collapse into one. Seed-phase tree-center gathers were
-                 * 31% of kernel cycles. */
-                uint32_t ts = 0;
-                if (c.lane < cnt) {
-                    const char* vp =
-                        (const char*)vec_at<T>(di, c.istage[c.lane]);
-                    const int nl =
-                        ((int)((unsigned)di.dim * sizeof(T)) + 127) >> 7;
-                    for (int l = 0; l < nl; l++)
-                        ts += (uint32_t)(uint8_t)vp[(size_t)l << 7];
-                }
-                stage_dists<T, DM>(c, cnt);
-                asm volatile("" :: "v"(ts));   /* sink after the staging so
-                                                  the touches and the first
-                                                  rounds overlap */
-                spt_warm_parents(c, cnt);
-                if (c.lane == 0)
-                    for (int i = 0; i < cnt; i++)
-                        ndheap_insert(c.spt, &c.ss->spt_count,
-                                      NodeDist{base + i, c.dstage[i]}, &c.ss->oflow);
-                __syncthreads();
-            }
+            for (int base = cs; base < ce; base += 64)
+                stage_children<T, DM>(c, base, min(64, ce - base));
+        }
+    }
+}
+
+/* ------------------------------------------------------------------ *
+ * graph traversal steps shared by the BKT, iterative and KDT kernels
+ * ------------------------------------------------------------------ */
+
+/* adjacency row of one node: lane i < deg holds neighbor i */
+struct Row {
+    int32_t nn;         /* this lane's neighbor id (-1 past deg) */
+    int firstneg;       /* first lane with no neighbor: the row ends there */
+    int32_t checkNode;  /* last slot: < -1 marks a duplicate chain */
+};
+
+template <typename T>
+DEV Row load_row(QCtx<T>& c, int32_t node)
+{
+    const int deg = c.di->deg;
+    const int32_t* row = c.di->graph + (size_t)node * deg;
+    Row r;
+    r.nn = c.lane < deg ? row[c.lane] : -1;
+    uint64_t negm = __ballot(c.lane >= deg || r.nn < 0);
+    r.firstneg = negm ? (int)__builtin_ctzll(negm) : 64;
+    r.checkNode = __shfl(r.nn, deg - 1);
+    return r;
+}
+
+/* neighbor expansion (BKTIndex.cpp:333-345): compact the unvisited
+ * neighbors of `r` (row order preserved) into istage[0..ncand) and return
+ * ncand; ends in a barrier.
+ * spec bit0: while the visited-CAS round is in flight, warm every
+ * neighbor's vector lines (one byte per 128B line) — the unvisited
+ * ones are exactly what stage_dists reads next, so the two
+ * dependent HBM round trips (CAS, vector gather) overlap; the
+ * re-visited rows were read recently and mostly hit L2/L3. */
+template <typename T>
+DEV int expand_neighbors(QCtx<T>& c, const Row& r)
+{
+    int already = 1;
+    uint32_t tsink = 0;
+    if (c.lane < r.firstneg) {
+        if (c.cfg->spec_flags & 1) tsink = touch_lines<T>(*c.di, r.nn);
+        already = visited_test_insert(c.vtab, c.vmask, r.nn, &c.ss->oflow);
+    }
+    uint64_t candm = __ballot(c.lane < r.firstneg && !already);
+    asm volatile("" :: "v"(tsink));
+    if ((candm >> c.lane) & 1) {
+        int pos = __popcll(candm & ((1ull << c.lane) - 1));
+        c.istage[pos] = r.nn;
+    }
+    __syncthreads();
+    return __popcll(candm);
+}
+
+/* spec bit1: lookahead on the next pop (perf-only — the frontier
+ * top rarely changes between here and the next iteration's pop).
+ * Read its adjacency row, probe the visited table READ-ONLY (first
+ * slot; stale/partial answers only cost an extra touch), and start
+ * the unvisited neighbors' vector loads. The loads stay in flight
+ * across the barrier — `sink` is consumed after the next pop. */
+template <typename T>
+DEV void lookahead_next(QCtx<T>& c, uint32_t& sink)
+{
+    if (!(c.cfg->spec_flags & 2)) return;
+    const int deg = c.di->deg;
+    if (c.lane == 0) c.ss->popped = ndheap_top(c.ng, c.ss->ng_count);
+    __syncthreads();
+    int32_t nxt = c.ss->popped.node;
+    if (nxt >= 0 && c.lane < deg) {
+        int32_t t = c.di->graph[(size_t)nxt * deg + c.lane];
+        if (t >= 0) {
+            uint32_t key = (uint32_t)(t + 1);
+            uint32_t h = (key * 2654435761u) & c.vmask;
+            if (c.vtab[h] != (int32_t)key) sink += touch_lines<T>(*c.di, t);
         }
     }
 }
@@ -642,12 +770,33 @@ DEV void init_search_trees_dev(QCtx<T>& c)
 #define SPTAG_LB_WAVES 1   /* min waves/SIMD hint; raise to cap VGPRs */
 #endif
 
-/* Per-phase cycle marks, diagnostic builds only (PROF template arg).
- * One wave per workgroup, so lane-0 clock64 spans are wave-accurate. */
-#define PMARK() do { if (PROF && lane == 0) pmark = clock64(); } while (0)
-#define PACC(i) do { if (PROF && lane == 0) { \
-        uint64_t now_ = clock64(); pc[i] += now_ - pmark; pmark = now_; } \
-    } while (0)
+/* Per-phase cycle marks, diagnostic builds only; every member is empty
+ * without PROF. One wave per workgroup, so lane-0 clock64 spans are
+ * wave-accurate. */
+template <bool PROF>
+struct PhaseClock {
+    uint64_t pc[10] = {};
+    uint64_t t = 0, ng = 0, t_ng = 0;
+    DEV void mark() { if (PROF && threadIdx.x == 0) t = clock64(); }
+    DEV void acc(int i)
+    {
+        if (PROF && threadIdx.x == 0) {
+            uint64_t now = clock64();
+            pc[i] += now - t;
+            t = now;
+        }
+    }
+    /* lane 0 only: NG-insert share of the `insert` phase */
+    DEV void ng_begin() { if (PROF) t_ng = clock64(); }
+    DEV void ng_end() { if (PROF) ng += clock64() - t_ng; }
+    DEV void store(int32_t* s) const   /* stats slots 2..15 */
+    {
+#pragma unroll
+        for (int i = 0; i < 10; i++) s[2 + i] = (int32_t)pc[i];
+        s[12] = (int32_t)ng;
+        s[13] = s[14] = s[15] = 0;
+    }
+};
 
 template <typename T, int DM, bool LDSHEAP, bool PROF = false>
 __global__ __launch_bounds__(64, SPTAG_LB_WAVES)
@@ -656,89 +805,48 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     const int q = blockIdx.x;
     if (q >= cfg.nq) return;
     const int lane = threadIdx.x;
-    uint64_t pc[10] = {};
-    uint64_t pmark = 0, pc_ng = 0;
+    PhaseClock<PROF> clk;
 
-    extern __shared__ char smem[];
-    size_t off = 0;
-    T* qlds = (T*)(smem + off);
-    off += ((size_t)di.dim * sizeof(T) + 15) & ~15ul;
-    float* dstage = (float*)(smem + off); off += MAX_DEG * 4;
-    int32_t* istage = (int32_t*)(smem + off); off += MAX_DEG * 4;
-    QRes* qrs = (QRes*)(smem + off); off += (size_t)cfg.k * 8;
-    float* dpq = (float*)(smem + off); off += ((size_t)cfg.dpq_cap + 1) * 4;
-    SerialState* ss = (SerialState*)(smem + off); off += 64;
-
+    const LdsLayout L = lds_layout(di.dim, sizeof(T), cfg.k, MAX_DEG, cfg.dpq_cap,
+                                   true, LDSHEAP ? cfg.ng_cap : 0);
     HeapRef ng, spt;
-    ng.cap = cfg.ng_cap;  ng.ref_cap = cfg.max_check * 30;   /* WorkSpace.h:265 */
-    ng.lds = nullptr; ng.lsplit = 0;
-    spt.cap = cfg.spt_cap; spt.ref_cap = cfg.max_check * 10;
-    /* SPT (tree) heap: hot top levels in an LDS tier, tail in global
-     * scratch — full reference capacity without the LDS cost of the whole
-     * heap (its all-global round-1 form made the seed phase 41.5% of
-     * kernel cycles). */
-    spt.a = (NodeDist*)bufs.gheap_spt + (size_t)q * (cfg.spt_cap + 1);
-    spt.lds = (NodeDist*)(smem + off); off += ((size_t)SPT_LDS_TIER + 1) * 8;
-    spt.lsplit = SPT_LDS_TIER;
-    if (LDSHEAP) {
-        ng.a = (NodeDist*)(smem + off); off += ((size_t)cfg.ng_cap + 1) * 8;
-    } else {
-        ng.a = (NodeDist*)bufs.gheap_ng + (size_t)q * (cfg.ng_cap + 1);
-    }
-
-    /* stage query */
-    const T* gq = (const T*)bufs.queries + (size_t)q * di.dim;
-    for (int i = lane; i < di.dim; i += 64) qlds[i] = gq[i];
-
-    if (lane == 0) {
-        ss->ng_count = 0; ss->spt_count = 0; ss->dpq_len = 1; ss->checked = 0;
-        ss->oflow = 0; ss->terminate = 0; ss->break_flag = 0; ss->want_tree = 0;
-        ng.a[0] = NodeDist{-1, MAXDIST};   /* Heap empty-top sentinel */
-        hset(spt, 0, NodeDist{-1, MAXDIST});
-        dpq[0] = MAXDIST;                  /* DistPriorityQueue seed element */
-        for (int i = 0; i < cfg.k; i++) qrs[i] = QRes{-1, MAXDIST};
-    }
-    __syncthreads();
-
-    QCtx<T> c{&di, &cfg, qlds, dstage, istage, qrs, dpq, ng, spt,
-              bufs.visited + (size_t)q * cfg.vcap, (uint32_t)(cfg.vcap - 1),
-              ss, lane};
+    search_heaps<LDSHEAP>(cfg, bufs, L, q, ng, spt);
+    QCtx<T> c = begin_query<T>(&di, &cfg, L, bufs.queries, q, cfg.k, nullptr, ng, spt,
+                               bufs.visited, cfg.vcap, SerialState{}, true);
+    SerialState* ss = c.ss;
+    QRes* qrs = c.qrs;
+    float* dpq = c.dpq;
 
     /* DistPriorityQueue (WorkSpace.h:167-225) as a FLAT bounded max-set:
      * its observable behavior (the kept multiset and its current maximum)
      * is independent of heap layout, so the m_Results state here is an
-     * unordered LDS array + uniform registers replicated wave-wide. */
+     * unordered LDS array + uniform registers replicated wave-wide; slot 0
+     * starts as the queue's MaxDist seed element. */
+    if (lane == 0) dpq[0] = MAXDIST;
     float dmax = MAXDIST;
     int dlen = 1, dargmax = 0;
 
-    PMARK();
+    clk.mark();
     init_search_trees_dev<T, DM>(c);
     __syncthreads();
     search_trees_dev<T, DM>(c, cfg.init_pivots);
-    PACC(0);
+    clk.acc(0);
 
-    const int deg = di.deg;
-    const int checkPos = deg - 1;
-    const int nline = ((int)((unsigned)di.dim * sizeof(T)) + 127) >> 7;
     int popped = 0;
     uint32_t spec_sink = 0;   /* keeps lookahead loads alive across barriers */
 
     for (;;) {
         __syncthreads();
         if (ss->ng_count <= 0 || ss->terminate || ss->oflow) break;
-        PMARK();
+        clk.mark();
         if (lane == 0) ss->popped = ndheap_pop(c.ng, &ss->ng_count);
         __syncthreads();
-        PACC(1);
+        clk.acc(1);
         asm volatile("" :: "v"(spec_sink));   /* lookahead loads land here */
         popped++;
         NodeDist gnode = ss->popped;
-        const int32_t* row = di.graph + (size_t)gnode.node * deg;
-        int32_t nn = lane < deg ? row[lane] : -1;
-        uint64_t negm = __ballot(lane >= deg || nn < 0);
-        int firstneg = negm ? (int)__builtin_ctzll(negm) : 64;
-        int32_t checkNode = __shfl(nn, checkPos);
-        PACC(2);
+        const Row row = load_row(c, gnode.node);
+        clk.acc(2);
 
         if (lane == 0) {
             /* BKTIndex.cpp:290-331: result/termination block. The dispatch
@@ -747,8 +855,8 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
              * the duplicate chain until AddPoint rejects) vs NeverDup (add
              * the center only). */
             if (gnode.distance <= qrs[0].dist) {
-                if (checkNode < -1) {
-                    const int32_t* tn = &di.tree_nodes[(size_t)(-2 - checkNode) * 3];
+                if (row.checkNode < -1) {
+                    const int32_t* tn = &di.tree_nodes[(size_t)(-2 - row.checkNode) * 3];
                     int32_t i = -tn[1];
                     int32_t tmpNode = gnode.node;
                     do {
@@ -775,44 +883,20 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
             }
         }
         __syncthreads();
-        PACC(3);
+        clk.acc(3);
         if (ss->terminate) break;
 
-        /* neighbor expansion (BKTIndex.cpp:333-345): compact the unvisited
-         * neighbors (row order preserved) and stage their distances.
-         * spec bit0: while the visited-CAS round is in flight, warm every
-         * neighbor's vector lines (one byte per 128B line) — the unvisited
-         * ones are exactly what stage_dists reads next, so the two
-         * dependent HBM round trips (CAS, vector gather) overlap; the
-         * re-visited rows were read recently and mostly hit L2/L3. */
-        int already = 1;
-        uint32_t tsink = 0;
-        if (lane < firstneg) {
-            if (cfg.spec_flags & 1) {
-                const char* vp = (const char*)vec_at<T>(di, nn);
-                for (int l = 0; l < nline; l++)
-                    tsink += (uint32_t)(uint8_t)vp[(size_t)l << 7];
-            }
-            already = visited_test_insert(c.vtab, c.vmask, nn, &ss->oflow);
-        }
-        uint64_t candm = __ballot(lane < firstneg && !already);
-        asm volatile("" :: "v"(tsink));
-        int ncand = __popcll(candm);
-        if ((candm >> lane) & 1) {
-            int pos = __popcll(candm & ((1ull << lane) - 1));
-            istage[pos] = nn;
-        }
-        __syncthreads();
-        PACC(4);
+        int ncand = expand_neighbors(c, row);
+        clk.acc(4);
         stage_dists<T, DM>(c, ncand);
-        PACC(5);
+        clk.acc(5);
         /* insert phase (BKTIndex.cpp:337-344). m_Results (the flat max-set)
          * appends in O(1); a replace costs one wave-parallel max rescan
          * (any max-valued slot may be replaced — same multiset). The NG
          * frontier heap stays an exact Heap.h emulation on lane 0: its pop
          * order on equal keys is part of the parity contract. */
         for (int r = 0; r < ncand; r++) {
-            float dv = dstage[r];
+            float dv = c.dstage[r];
             if (lane == 0) ss->checked++;
             if (!(dv > dmax)) {
                 if (dlen < cfg.dpq_cap) {
@@ -836,15 +920,10 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
                     dargmax = __shfl(mi, 0);
                 }
                 if (lane == 0) {
-                    if (PROF) {
-                        uint64_t t0_ = clock64();
-                        ndheap_insert(c.ng, &ss->ng_count,
-                                      NodeDist{istage[r], dv}, &ss->oflow);
-                        pc_ng += clock64() - t0_;
-                    } else {
-                        ndheap_insert(c.ng, &ss->ng_count,
-                                      NodeDist{istage[r], dv}, &ss->oflow);
-                    }
+                    clk.ng_begin();
+                    ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], dv},
+                                  &ss->oflow);
+                    clk.ng_end();
                 }
             }
         }
@@ -854,61 +933,24 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
                              ndheap_top(c.spt, ss->spt_count).distance);
         }
         __syncthreads();
-        PACC(6);
+        clk.acc(6);
         if (ss->want_tree)
             search_trees_dev<T, DM>(c, cfg.other_pivots + ss->checked);
-        PACC(7);
-        /* spec bit1: lookahead on the next pop (perf-only — the frontier
-         * top rarely changes between here and the next iteration's pop).
-         * Read its adjacency row, probe the visited table READ-ONLY (first
-         * slot; stale/partial answers only cost an extra touch), and start
-         * the unvisited neighbors' vector loads. The loads stay in flight
-         * across the barrier — spec_sink is consumed after the next pop. */
-        if (cfg.spec_flags & 2) {
-            if (lane == 0) ss->popped = ndheap_top(c.ng, ss->ng_count);
-            __syncthreads();
-            int32_t nxt = ss->popped.node;
-            if (nxt >= 0 && lane < deg) {
-                int32_t t = di.graph[(size_t)nxt * deg + lane];
-                if (t >= 0) {
-                    uint32_t key = (uint32_t)(t + 1);
-                    uint32_t h = (key * 2654435761u) & c.vmask;
-                    if (c.vtab[h] != (int32_t)key) {
-                        const char* vp = (const char*)vec_at<T>(di, t);
-                        for (int l = 0; l < nline; l++)
-                            spec_sink += (uint32_t)(uint8_t)vp[(size_t)l << 7];
-                    }
-                }
-            }
-        }
-        PACC(8);
+        clk.acc(7);
+        lookahead_next(c, spec_sink);
+        clk.acc(8);
     }
     __syncthreads();
 
-    if (lane == 0) {
-        bufs.oflow[q] = ss->oflow;
-        PMARK();
-        qrs_sort(qrs, cfg.k);
-        PACC(9);
-        if (bufs.stats) {
-            if (PROF) {
-                int32_t* s = bufs.stats + (size_t)q * PROF_STATS;
-                s[0] = ss->checked;
-                s[1] = popped;
-#pragma unroll
-                for (int i = 0; i < 10; i++) s[2 + i] = (int32_t)pc[i];
-                s[12] = (int32_t)pc_ng;   /* NG-insert share of `insert` */
-                s[13] = s[14] = s[15] = 0;
-            } else {
-                bufs.stats[(size_t)q * 2 + 0] = ss->checked;
-                bufs.stats[(size_t)q * 2 + 1] = popped;
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = lane; i < cfg.k; i += 64) {
-        bufs.out_vids[(size_t)q * cfg.k + i] = qrs[i].vid;
-        bufs.out_dists[(size_t)q * cfg.k + i] = qrs[i].dist;
+    if (lane == 0) bufs.oflow[q] = ss->oflow;
+    clk.mark();
+    write_topk(qrs, cfg.k, q, bufs.out_vids, bufs.out_dists);
+    clk.acc(9);
+    if (lane == 0 && bufs.stats) {
+        int32_t* s = bufs.stats + (size_t)q * (PROF ? (int)PROF_STATS : 2);
+        s[0] = ss->checked;
+        s[1] = popped;
+        if constexpr (PROF) clk.store(s);
     }
 }
 
@@ -929,15 +971,6 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
     if (q >= cfg.nq) return;
     const int lane = threadIdx.x;
 
-    extern __shared__ char smem[];
-    size_t off = 0;
-    T* qlds = (T*)(smem + off);
-    off += ((size_t)di.dim * sizeof(T) + 15) & ~15ul;
-    float* dstage = (float*)(smem + off); off += MAX_DEG * 4;
-    int32_t* istage = (int32_t*)(smem + off); off += MAX_DEG * 4;
-    QRes* qrs = (QRes*)(smem + off); off += (size_t)batch * 8;
-    SerialState* ss = (SerialState*)(smem + off); off += 64;
-
     float* dpq = ib.dpq + (size_t)q * (cfg.dpq_cap + 1);
     HeapRef ng, spt;
     ng.cap = cfg.ng_cap;  ng.ref_cap = cfg.ng_cap;   /* reference capacities */
@@ -948,33 +981,22 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
     ng.a = (NodeDist*)ib.gheap_ng + (size_t)q * (cfg.ng_cap + 1);
     spt.a = (NodeDist*)ib.gheap_spt + (size_t)q * (cfg.spt_cap + 1);
 
-    const T* gq = (const T*)ib.queries + (size_t)q * di.dim;
-    for (int i = lane; i < di.dim; i += 64) qlds[i] = gq[i];
-
     IterState st = ib.state[q];
-    if (lane == 0) {
-        ss->ng_count = st.ng_count;
-        ss->spt_count = st.spt_count;
-        ss->oflow = st.oflow;
-        /* ResetResult (WorkSpace.h:276): fresh m_Results + zeroed counters;
-         * queues, visited set and the sticky relaxed flag persist. */
-        ss->dpq_len = 1;
-        dpq[1] = MAXDIST;
-        ss->checked = 0;
-        ss->tree_checked = 0;
-        ss->terminate = 0; ss->break_flag = 0; ss->want_tree = 0;
-        ss->no_better = st.relaxed;      /* reuse slot: sticky relaxedMono */
-        for (int i = 0; i < batch; i++) qrs[i] = QRes{-1, MAXDIST};
-        if (st.first) {
-            ng.a[0] = NodeDist{-1, MAXDIST};
-            spt.a[0] = NodeDist{-1, MAXDIST};
-        }
-    }
-    __syncthreads();
+    /* ResetResult (WorkSpace.h:276): fresh m_Results + zeroed counters;
+     * queues, visited set and the sticky relaxed flag persist. */
+    SerialState ss0{};
+    ss0.ng_count = st.ng_count;
+    ss0.spt_count = st.spt_count;
+    ss0.oflow = st.oflow;
+    ss0.relaxed = st.relaxed;
+    ss0.dpq_len = 1;
+    if (lane == 0) dpq[1] = MAXDIST;
 
-    QCtx<T> c{&di, &cfg, qlds, dstage, istage, qrs, dpq, ng, spt,
-              ib.visited + (size_t)q * cfg.vcap, (uint32_t)(cfg.vcap - 1),
-              ss, lane};
+    QCtx<T> c = begin_query<T>(&di, &cfg, iter_lds_layout(di.dim, sizeof(T), batch),
+                               ib.queries, q, batch, dpq, ng, spt, ib.visited,
+                               cfg.vcap, ss0, st.first);
+    SerialState* ss = c.ss;
+    QRes* qrs = c.qrs;
 
     if (st.first) {
         init_search_trees_dev<T, DM>(c);
@@ -982,8 +1004,6 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
         search_trees_dev<T, DM>(c, cfg.init_pivots);
     }
 
-    const int deg = di.deg;
-    const int checkPos = deg - 1;
     int count = 0;
 
     for (;;) {
@@ -992,11 +1012,7 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
         if (lane == 0) ss->popped = ndheap_pop(c.ng, &ss->ng_count);
         __syncthreads();
         NodeDist gnode = ss->popped;
-        const int32_t* row = di.graph + (size_t)gnode.node * deg;
-        int32_t nn = lane < deg ? row[lane] : -1;
-        uint64_t negm = __ballot(lane >= deg || nn < 0);
-        int firstneg = negm ? (int)__builtin_ctzll(negm) : 64;
-        int32_t checkNode = __shfl(nn, checkPos);
+        const Row row = load_row(c, gnode.node);
 
         if (lane == 0) {
             int cnt_new = count;
@@ -1004,64 +1020,41 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
                 qrs_add(qrs, batch, gnode.node, gnode.distance);
                 cnt_new = count + 1;
                 if (gnode.distance > dpq[1] || ss->checked > cfg.max_check)
-                    ss->no_better = 1;                   /* relaxedMono */
+                    ss->relaxed = 1;                     /* relaxedMono */
             }
             ss->fbcast = __int_as_float(cnt_new);
         }
         __syncthreads();
         count = __float_as_int(ss->fbcast);
 
-        if (checkNode < -1) {
+        if (row.checkNode < -1) {
             /* iterative duplicate chain (BKTIndex.cpp:387-405): duplicates
              * enter the frontier; stage chunk distances, lane 0 inserts */
-            const int32_t* tn = &di.tree_nodes[(size_t)(-2 - checkNode) * 3];
+            const int32_t* tn = &di.tree_nodes[(size_t)(-2 - row.checkNode) * 3];
             int32_t cs0 = -tn[1], ce0 = tn[2];
             for (int base = cs0; base < ce0; base += 64) {
                 int cnt = min(64, ce0 - base);
-                if (lane < cnt)
-                    istage[lane] = di.tree_nodes[(size_t)(base + lane) * 3];
-                __syncthreads();
-                stage_dists<T, DM>(c, cnt);
+                stage_child_dists<T, DM, false>(c, base, cnt);
                 if (lane == 0) {
                     for (int i = 0; i < cnt; i++) {
-                        int32_t tmpNode = istage[i];
+                        int32_t tmpNode = c.istage[i];
                         if (!not_deleted(di, tmpNode)) continue;
                         if (!visited_test_insert(c.vtab, c.vmask, tmpNode, &ss->oflow))
                             ndheap_insert(c.ng, &ss->ng_count,
-                                          NodeDist{tmpNode, dstage[i]}, &ss->oflow);
+                                          NodeDist{tmpNode, c.dstage[i]}, &ss->oflow);
                     }
                 }
                 __syncthreads();
             }
         }
 
-        /* spec bit0 (see bkt kernel): warm neighbor vector lines during
-         * the visited-CAS round. */
-        int already = 1;
-        uint32_t tsink = 0;
-        if (lane < firstneg) {
-            if (cfg.spec_flags & 1) {
-                const char* vp = (const char*)vec_at<T>(di, nn);
-                const int nline = ((int)((unsigned)di.dim * sizeof(T)) + 127) >> 7;
-                for (int l = 0; l < nline; l++)
-                    tsink += (uint32_t)(uint8_t)vp[(size_t)l << 7];
-            }
-            already = visited_test_insert(c.vtab, c.vmask, nn, &ss->oflow);
-        }
-        uint64_t candm = __ballot(lane < firstneg && !already);
-        asm volatile("" :: "v"(tsink));
-        int ncand = __popcll(candm);
-        if ((candm >> lane) & 1) {
-            int pos = __popcll(candm & ((1ull << lane) - 1));
-            istage[pos] = nn;
-        }
-        __syncthreads();
+        int ncand = expand_neighbors(c, row);
         stage_dists<T, DM>(c, ncand);
         if (lane == 0) {
             for (int r = 0; r < ncand; r++) {
-                float dv = dstage[r];
+                float dv = c.dstage[r];
                 ss->checked++;
-                ndheap_insert(c.ng, &ss->ng_count, NodeDist{istage[r], dv}, &ss->oflow);
+                ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], dv}, &ss->oflow);
                 dpq_insert(dpq, &ss->dpq_len, cfg.dpq_cap, dv);
             }
             ss->want_tree = (ndheap_top(c.ng, ss->ng_count).distance >
@@ -1074,23 +1067,18 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
     __syncthreads();
 
     if (lane == 0) {
-        qrs_sort(qrs, batch);
         st.ng_count = ss->ng_count;
         st.spt_count = ss->spt_count;
         st.checked = ss->checked;
         st.tree_checked = ss->tree_checked;
-        st.relaxed = ss->no_better;
+        st.relaxed = ss->relaxed;
         st.first = 0;
         st.oflow = ss->oflow;
         ib.state[q] = st;
         ib.out_counts[q] = count;
         ib.out_relaxed[q] = st.relaxed;
     }
-    __syncthreads();
-    for (int i = lane; i < batch; i += 64) {
-        ib.out_vids[(size_t)q * batch + i] = qrs[i].vid;
-        ib.out_dists[(size_t)q * batch + i] = qrs[i].dist;
-    }
+    write_topk(qrs, batch, q, ib.out_vids, ib.out_dists);
 }
 
 /* ------------------------------------------------------------------ *
@@ -1169,54 +1157,22 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     if (q >= cfg.nq) return;
     const int lane = threadIdx.x;
 
-    extern __shared__ char smem[];
-    size_t off = 0;
-    T* qlds = (T*)(smem + off);
-    off += ((size_t)di.dim * sizeof(T) + 15) & ~15ul;
-    float* dstage = (float*)(smem + off); off += MAX_DEG * 4;
-    int32_t* istage = (int32_t*)(smem + off); off += MAX_DEG * 4;
-    QRes* qrs = (QRes*)(smem + off); off += (size_t)cfg.k * 8;
-    float* dpq = (float*)(smem + off); off += ((size_t)cfg.dpq_cap + 1) * 4;
-    SerialState* ss = (SerialState*)(smem + off); off += 64;
-
+    /* same layout as the BKT kernel; the results-queue region is reserved
+     * but unused here (KDT has no results-queue gate) */
+    const LdsLayout L = lds_layout(di.dim, sizeof(T), cfg.k, MAX_DEG, cfg.dpq_cap,
+                                   true, LDSHEAP ? cfg.ng_cap : 0);
     HeapRef ng, spt;
-    ng.cap = cfg.ng_cap;  ng.ref_cap = cfg.max_check * 30;
-    ng.lds = nullptr; ng.lsplit = 0;
-    spt.cap = cfg.spt_cap; spt.ref_cap = cfg.max_check * 10;
-    spt.a = (NodeDist*)bufs.gheap_spt + (size_t)q * (cfg.spt_cap + 1);
-    spt.lds = (NodeDist*)(smem + off); off += ((size_t)SPT_LDS_TIER + 1) * 8;
-    spt.lsplit = SPT_LDS_TIER;
-    if (LDSHEAP) {
-        ng.a = (NodeDist*)(smem + off); off += ((size_t)cfg.ng_cap + 1) * 8;
-    } else {
-        ng.a = (NodeDist*)bufs.gheap_ng + (size_t)q * (cfg.ng_cap + 1);
-    }
-
-    const T* gq = (const T*)bufs.queries + (size_t)q * di.dim;
-    for (int i = lane; i < di.dim; i += 64) qlds[i] = gq[i];
-
-    if (lane == 0) {
-        ss->ng_count = 0; ss->spt_count = 0; ss->dpq_len = 1; ss->checked = 0;
-        ss->oflow = 0; ss->terminate = 0; ss->break_flag = 0; ss->want_tree = 0;
-        ss->tree_checked = 0; ss->no_better = 0;
-        ng.a[0] = NodeDist{-1, MAXDIST};
-        hset(spt, 0, NodeDist{-1, MAXDIST});
-        dpq[1] = MAXDIST;
-        for (int i = 0; i < cfg.k; i++) qrs[i] = QRes{-1, MAXDIST};
-    }
-    __syncthreads();
-
-    QCtx<T> c{&di, &cfg, qlds, dstage, istage, qrs, dpq, ng, spt,
-              bufs.visited + (size_t)q * cfg.vcap, (uint32_t)(cfg.vcap - 1),
-              ss, lane};
+    search_heaps<LDSHEAP>(cfg, bufs, L, q, ng, spt);
+    QCtx<T> c = begin_query<T>(&di, &cfg, L, bufs.queries, q, cfg.k, nullptr, ng, spt,
+                               bufs.visited, cfg.vcap, SerialState{}, true);
+    SerialState* ss = c.ss;
+    QRes* qrs = c.qrs;
 
     /* InitSearchTrees (KDTree.h:213): every tree root at bound 0 */
     for (int t = 0; t < di.ntrees; t++)
         kdt_search_node_dev<T, DM>(c, di.tree_start[t], 0.0f);
     kdt_search_trees_dev<T, DM>(c, cfg.init_pivots);
 
-    const int deg = di.deg;
-    const int nline = ((int)((unsigned)di.dim * sizeof(T)) + 127) >> 7;
     int popped = 0;
     uint32_t spec_sink = 0;
 
@@ -1228,10 +1184,7 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         asm volatile("" :: "v"(spec_sink));
         popped++;
         NodeDist gnode = ss->popped;
-        const int32_t* row = di.graph + (size_t)gnode.node * deg;
-        int32_t nn = lane < deg ? row[lane] : -1;
-        uint64_t negm = __ballot(lane >= deg || nn < 0);
-        int firstneg = negm ? (int)__builtin_ctzll(negm) : 64;
+        const Row row = load_row(c, gnode.node);
 
         if (lane == 0) {
             /* KDTIndex.cpp:201-209: result + budget termination */
@@ -1247,36 +1200,17 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         if (ss->terminate) break;
         float upper_bound = ss->fbcast;
 
-        /* spec bit0 (see bkt kernel): warm neighbor vector lines during
-         * the visited-CAS round. */
-        int already = 1;
-        uint32_t tsink = 0;
-        if (lane < firstneg) {
-            if (cfg.spec_flags & 1) {
-                const char* vp = (const char*)vec_at<T>(di, nn);
-                for (int l = 0; l < nline; l++)
-                    tsink += (uint32_t)(uint8_t)vp[(size_t)l << 7];
-            }
-            already = visited_test_insert(c.vtab, c.vmask, nn, &ss->oflow);
-        }
-        uint64_t candm = __ballot(lane < firstneg && !already);
-        asm volatile("" :: "v"(tsink));
-        int ncand = __popcll(candm);
-        if ((candm >> lane) & 1) {
-            int pos = __popcll(candm & ((1ull << lane) - 1));
-            istage[pos] = nn;
-        }
-        __syncthreads();
+        int ncand = expand_neighbors(c, row);
         stage_dists<T, DM>(c, ncand);
         if (lane == 0) {
             /* KDTIndex.cpp:211-233: every computed neighbor joins the
              * frontier; track whether any beat the upper bound */
             int local_opt = 1;
             for (int r = 0; r < ncand; r++) {
-                float dv = dstage[r];
+                float dv = c.dstage[r];
                 if (dv <= upper_bound) local_opt = 0;
                 ss->checked++;
-                ndheap_insert(c.ng, &ss->ng_count, NodeDist{istage[r], dv}, &ss->oflow);
+                ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], dv}, &ss->oflow);
             }
             if (local_opt) ss->no_better++;
             else ss->no_better = 0;
@@ -1293,24 +1227,7 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         if (ss->break_flag) break;
         if (ss->want_tree)
             kdt_search_trees_dev<T, DM>(c, cfg.other_pivots + ss->checked);
-        /* spec bit1 (see bkt kernel): next-pop lookahead. */
-        if (cfg.spec_flags & 2) {
-            if (lane == 0) ss->popped = ndheap_top(c.ng, ss->ng_count);
-            __syncthreads();
-            int32_t nxt = ss->popped.node;
-            if (nxt >= 0 && lane < deg) {
-                int32_t t = di.graph[(size_t)nxt * deg + lane];
-                if (t >= 0) {
-                    uint32_t key = (uint32_t)(t + 1);
-                    uint32_t h = (key * 2654435761u) & c.vmask;
-                    if (c.vtab[h] != (int32_t)key) {
-                        const char* vp = (const char*)vec_at<T>(di, t);
-                        for (int l = 0; l < nline; l++)
-                            spec_sink += (uint32_t)(uint8_t)vp[(size_t)l << 7];
-                    }
-                }
-            }
-        }
+        lookahead_next(c, spec_sink);
     }
     __syncthreads();
 
@@ -1320,13 +1237,8 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
             bufs.stats[(size_t)q * 2 + 0] = ss->checked;
             bufs.stats[(size_t)q * 2 + 1] = popped;
         }
-        qrs_sort(qrs, cfg.k);
     }
-    __syncthreads();
-    for (int i = lane; i < cfg.k; i += 64) {
-        bufs.out_vids[(size_t)q * cfg.k + i] = qrs[i].vid;
-        bufs.out_dists[(size_t)q * cfg.k + i] = qrs[i].dist;
-    }
+    write_topk(qrs, cfg.k, q, bufs.out_vids, bufs.out_dists);
 }
 
 /* ------------------------------------------------------------------ *
@@ -1344,54 +1256,44 @@ void truth_kernel(DevIndex di, const void* queries, int32_t nq, int32_t k,
     if (q >= nq) return;
     const int lane = threadIdx.x;
 
-    extern __shared__ char smem[];
-    size_t off = 0;
-    T* qlds = (T*)(smem + off);
-    off += ((size_t)di.dim * sizeof(T) + 15) & ~15ul;
-    QRes* qrs = (QRes*)(smem + off); off += (size_t)k * 8;
-    float* dstage = (float*)(smem + off);
-
-    const T* gq = (const T*)queries + (size_t)q * di.dim;
-    for (int i = lane; i < di.dim; i += 64) qlds[i] = gq[i];
-    if (lane == 0)
-        for (int i = 0; i < k; i++) qrs[i] = QRes{-1, MAXDIST};
-    __syncthreads();
+    QCtx<T> c = begin_query<T>(&di, nullptr, truth_lds_layout(di.dim, sizeof(T), k),
+                               queries, q, k, nullptr, HeapRef{}, HeapRef{}, nullptr, 0,
+                               SerialState{}, false);
+    /* no traversal state here: the scalar slot stages the 4 distances */
+    float* dstage = (float*)c.ss;
 
     for (int32_t base = 0; base < di.n; base += 4) {
         int cnt = min(4, di.n - base);
         int j = lane >> 4;
         if (j < cnt) {
-            float dv = ref_dist_grp<T, DM>(qlds, vec_at<T>(di, base + j), di.dim);
+            float dv = ref_dist_grp<T, DM>(c.qlds, vec_at<T>(di, base + j), di.dim);
             if ((lane & 15) == 0) dstage[j] = dv;
         }
         __syncthreads();
         if (lane == 0) {
             for (int i = 0; i < cnt; i++) {
                 if (di.has_deleted && di.deleted[base + i]) continue;
-                qrs_add(qrs, k, base + i, dstage[i]);
+                qrs_add(c.qrs, k, base + i, dstage[i]);
             }
         }
         __syncthreads();
     }
-    if (lane == 0) qrs_sort(qrs, k);
-    __syncthreads();
-    for (int i = lane; i < k; i += 64) {
-        out_vids[(size_t)q * k + i] = qrs[i].vid;
-        out_dists[(size_t)q * k + i] = qrs[i].dist;
-    }
+    write_topk(c.qrs, k, q, out_vids, out_dists);
 }
 
 /* ------------------------------------------------------------------ *
- * row gather/scatter (flagged-query reruns)
+ * row gather/scatter (flagged-query reruns): copy nrows rows, with idx
+ * naming the source rows (SRC_INDEXED, gather) or the destination rows
  * ------------------------------------------------------------------ */
 
-__global__ void gather_rows_kernel(char* dst, const char* src, int row_bytes,
-                                   const int32_t* idx, int nrows)
+template <bool SRC_INDEXED>
+__global__ void copy_rows_kernel(char* dst, const char* src, int row_bytes,
+                                 const int32_t* idx, int nrows)
 {
     int r = blockIdx.x;
     if (r >= nrows) return;
-    const char* s = src + (size_t)idx[r] * row_bytes;
-    char* d = dst + (size_t)r * row_bytes;
+    const char* s = src + (size_t)(SRC_INDEXED ? idx[r] : r) * row_bytes;
+    char* d = dst + (size_t)(SRC_INDEXED ? r : idx[r]) * row_bytes;
     if ((row_bytes & 3) == 0) {
         for (int i = threadIdx.x; i < row_bytes / 4; i += blockDim.x)
             ((uint32_t*)d)[i] = ((const uint32_t*)s)[i];
@@ -1401,43 +1303,46 @@ __global__ void gather_rows_kernel(char* dst, const char* src, int row_bytes,
     }
 }
 
-__global__ void scatter_rows_kernel(char* dst, const char* src, int row_bytes,
-                                    const int32_t* idx, int nrows)
+template <bool SRC_INDEXED>
+static int launch_copy_rows(void* dst, const void* src, int row_bytes,
+                            const int32_t* d_idx, int nrows, void* stream)
 {
-    int r = blockIdx.x;
-    if (r >= nrows) return;
-    const char* s = src + (size_t)r * row_bytes;
-    char* d = dst + (size_t)idx[r] * row_bytes;
-    if ((row_bytes & 3) == 0) {
-        for (int i = threadIdx.x; i < row_bytes / 4; i += blockDim.x)
-            ((uint32_t*)d)[i] = ((const uint32_t*)s)[i];
-    } else {
-        for (int i = threadIdx.x; i < row_bytes; i += blockDim.x)
-            d[i] = s[i];
-    }
+    hipLaunchKernelGGL(copy_rows_kernel<SRC_INDEXED>, dim3(nrows), dim3(64), 0,
+                       (hipStream_t)stream, (char*)dst, (const char*)src,
+                       row_bytes, d_idx, nrows);
+    return (int)hipGetLastError();
 }
 
 int launch_gather_rows(void* dst, const void* src, int row_bytes,
                        const int32_t* d_idx, int nrows, void* stream)
 {
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(nrows), dim3(64), 0,
-                       (hipStream_t)stream, (char*)dst, (const char*)src,
-                       row_bytes, d_idx, nrows);
-    return (int)hipGetLastError();
+    return launch_copy_rows<true>(dst, src, row_bytes, d_idx, nrows, stream);
 }
 
 int launch_scatter_rows(void* dst, const void* src, int row_bytes,
                         const int32_t* d_idx, int nrows, void* stream)
 {
-    hipLaunchKernelGGL(scatter_rows_kernel, dim3(nrows), dim3(64), 0,
-                       (hipStream_t)stream, (char*)dst, (const char*)src,
-                       row_bytes, d_idx, nrows);
-    return (int)hipGetLastError();
+    return launch_copy_rows<false>(dst, src, row_bytes, d_idx, nrows, stream);
 }
 
 /* ------------------------------------------------------------------ *
  * launchers
  * ------------------------------------------------------------------ */
+
+template <typename T> struct TypeTag { using type = T; };
+
+/* call f(TypeTag<T>, integral_constant<DM>) for the runtime (vt, dm) */
+template <typename F>
+static int dispatch_vt_dm(int vt, int dm, F&& f)
+{
+    using L2 = std::integral_constant<int, DM_L2>;
+    using Cos = std::integral_constant<int, DM_COSINE>;
+    if (vt == VT_FLOAT && dm == DM_L2) return f(TypeTag<float>{}, L2{});
+    if (vt == VT_FLOAT && dm == DM_COSINE) return f(TypeTag<float>{}, Cos{});
+    if (vt == VT_INT8 && dm == DM_L2) return f(TypeTag<int8_t>{}, L2{});
+    if (vt == VT_INT8 && dm == DM_COSINE) return f(TypeTag<int8_t>{}, Cos{});
+    return (int)hipErrorInvalidValue;
+}
 
 template <typename T, int DM, bool LDSHEAP>
 static int launch_one(const DevIndex& di, const SearchCfg& cfg,
@@ -1460,63 +1365,37 @@ static int launch_one(const DevIndex& di, const SearchCfg& cfg,
 int launch_bkt_search(int vt, int dm, bool heaps_in_lds, const DevIndex& di,
                       const SearchCfg& cfg, const SearchBufs& bufs, void* stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (vt == VT_FLOAT && dm == DM_L2)
-        return heaps_in_lds ? launch_one<float, DM_L2, true>(di, cfg, bufs, s)
-                            : launch_one<float, DM_L2, false>(di, cfg, bufs, s);
-    if (vt == VT_FLOAT && dm == DM_COSINE)
-        return heaps_in_lds ? launch_one<float, DM_COSINE, true>(di, cfg, bufs, s)
-                            : launch_one<float, DM_COSINE, false>(di, cfg, bufs, s);
-    if (vt == VT_INT8 && dm == DM_L2)
-        return heaps_in_lds ? launch_one<int8_t, DM_L2, true>(di, cfg, bufs, s)
-                            : launch_one<int8_t, DM_L2, false>(di, cfg, bufs, s);
-    if (vt == VT_INT8 && dm == DM_COSINE)
-        return heaps_in_lds ? launch_one<int8_t, DM_COSINE, true>(di, cfg, bufs, s)
-                            : launch_one<int8_t, DM_COSINE, false>(di, cfg, bufs, s);
-    return (int)hipErrorInvalidValue;
-}
-
-template <typename T, int DM>
-static int launch_truth_one(const DevIndex& di, const void* queries, int32_t nq,
-                            int32_t k, int32_t* ov, float* od, hipStream_t s)
-{
-    size_t lds = (((size_t)di.dim * sizeof(T) + 15) & ~15ul) + (size_t)k * 8 + 64;
-    hipLaunchKernelGGL((truth_kernel<T, DM>), dim3(nq), dim3(64), lds, s,
-                       di, queries, nq, k, ov, od);
-    return (int)hipGetLastError();
-}
-
-template <typename T, int DM>
-static int launch_iter_one(const DevIndex& di, const SearchCfg& cfg,
-                           const IterBufs& ib, int batch, hipStream_t s)
-{
-    size_t lds = (((size_t)di.dim * sizeof(T) + 15) & ~15ul) + MAX_DEG * 8 +
-                 (size_t)batch * 8 + 64;
-    hipLaunchKernelGGL((bkt_iter_kernel<T, DM>), dim3(cfg.nq), dim3(64), lds, s,
-                       di, cfg, ib, batch);
-    return (int)hipGetLastError();
+    return dispatch_vt_dm(vt, dm, [&](auto t, auto d) {
+        using T = typename decltype(t)::type;
+        constexpr int DM = decltype(d)::value;
+        hipStream_t s = (hipStream_t)stream;
+        return heaps_in_lds ? launch_one<T, DM, true>(di, cfg, bufs, s)
+                            : launch_one<T, DM, false>(di, cfg, bufs, s);
+    });
 }
 
 int launch_bkt_iter(int vt, int dm, const DevIndex& di, const SearchCfg& cfg,
                     const IterBufs& ib, int batch, void* stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (vt == VT_FLOAT && dm == DM_L2) return launch_iter_one<float, DM_L2>(di, cfg, ib, batch, s);
-    if (vt == VT_FLOAT && dm == DM_COSINE) return launch_iter_one<float, DM_COSINE>(di, cfg, ib, batch, s);
-    if (vt == VT_INT8 && dm == DM_L2) return launch_iter_one<int8_t, DM_L2>(di, cfg, ib, batch, s);
-    if (vt == VT_INT8 && dm == DM_COSINE) return launch_iter_one<int8_t, DM_COSINE>(di, cfg, ib, batch, s);
-    return (int)hipErrorInvalidValue;
+    return dispatch_vt_dm(vt, dm, [&](auto t, auto d) {
+        using T = typename decltype(t)::type;
+        size_t lds = iter_lds_layout(di.dim, sizeof(T), batch).total;
+        hipLaunchKernelGGL((bkt_iter_kernel<T, decltype(d)::value>), dim3(cfg.nq),
+                           dim3(64), lds, (hipStream_t)stream, di, cfg, ib, batch);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_truth(int vt, int dm, const DevIndex& di, const void* queries,
                  int32_t nq, int32_t k, int32_t* ov, float* od, void* stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (vt == VT_FLOAT && dm == DM_L2) return launch_truth_one<float, DM_L2>(di, queries, nq, k, ov, od, s);
-    if (vt == VT_FLOAT && dm == DM_COSINE) return launch_truth_one<float, DM_COSINE>(di, queries, nq, k, ov, od, s);
-    if (vt == VT_INT8 && dm == DM_L2) return launch_truth_one<int8_t, DM_L2>(di, queries, nq, k, ov, od, s);
-    if (vt == VT_INT8 && dm == DM_COSINE) return launch_truth_one<int8_t, DM_COSINE>(di, queries, nq, k, ov, od, s);
-    return (int)hipErrorInvalidValue;
+    return dispatch_vt_dm(vt, dm, [&](auto t, auto d) {
+        using T = typename decltype(t)::type;
+        size_t lds = truth_lds_layout(di.dim, sizeof(T), k).total;
+        hipLaunchKernelGGL((truth_kernel<T, decltype(d)::value>), dim3(nq), dim3(64),
+                           lds, (hipStream_t)stream, di, queries, nq, k, ov, od);
+        return (int)hipGetLastError();
+    });
 }
 
 }  /* namespace sptag_amd */
