@@ -125,6 +125,14 @@ int sptag_amd_truth(SptagAmdIndex* idx, const void* queries, int32_t nq,
 typedef struct SptagAmdIterBatch SptagAmdIterBatch;
 SptagAmdIterBatch* sptag_amd_iter_create(SptagAmdIndex* idx, const void* queries,
                                          int32_t nq, int32_t max_check);
+/* A count below `batch` means that query's iterator is exhausted, and only
+ * that. The per-query visited table is fixed at create time
+ * (next_pow2(max(4096, 4*max_check)) slots) while the reference's grows on
+ * demand and its iterator runs on past MaxCheck. On the call in which any
+ * query's table saturates, and on every later call of that batch, next()
+ * prints a line naming visited-table saturation to stderr and returns
+ * SPTAG_AMD_ERR_INTERNAL with the outputs untouched; every earlier call is
+ * exact. The table is not grown or re-sized. */
 int sptag_amd_iter_next(SptagAmdIterBatch* it, int32_t batch,
                         int32_t* out_vids, float* out_dists,
                         int32_t* out_counts, int32_t* out_relaxed);

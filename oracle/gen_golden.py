@@ -130,6 +130,62 @@ def gen_iter_and_add_goldens():
         import shutil
         shutil.copy(os.path.join(out, "graph.bin"),
                     os.path.join(d, "postadd_graph.bin"))
+    gen_cosine_add_goldens()
+
+
+COSINE_ADD = ["f32_cos_n10k_d48", "i8_cos_deg48"]
+NADD_COSINE = 16
+
+
+def read_default(path, dtype):
+    with open(path, "rb") as f:
+        n, dim = np.frombuffer(f.read(8), dtype=np.int32)
+        return np.frombuffer(f.read(), dtype=dtype).reshape(n, dim)
+
+
+def gen_cosine_add_goldens():
+    """Post-add state of the reference's own AddIndex on the cosine fixtures:
+    16 un-normalised vectors go in, the reference normalises them itself.
+    A whole post-add graph is larger than a committed file may be, so only
+    what the add changed is kept:
+      add16_vectors.bin      the 16 vectors as given to AddIndex
+      postadd16_vectors.bin  the last 16 rows of the saved vectors.bin,
+                             i.e. the reference's normalised form
+      postadd16_rows.bin     [int32 n_after][int32 degree][int32 nrows], then
+                             nrows * {int32 row id, int32 row[degree]}: every
+                             row of the saved graph.bin that is new or differs
+                             from index/graph.bin, in id order
+    The fixture's index folder is only read. Also reachable on its own as
+    `gen_golden.py cosine-add`, since main() would rebuild every index."""
+    import tempfile
+    for name in COSINE_ADD:
+        d = os.path.join(GOLDEN, name)
+        meta = json.load(open(os.path.join(d, "meta.json")))
+        dim = meta["dim"]
+        rng = np.random.default_rng(9000 + dim)
+        if meta["valuetype"] == "Float":
+            dtype = np.float32
+            add = (rng.standard_normal((NADD_COSINE, dim)) * 3).astype(np.float32)
+        else:
+            dtype = np.int8
+            add = rng.integers(-100, 101, (NADD_COSINE, dim)).astype(np.int8)
+        write_default(os.path.join(d, "add16_vectors.bin"), add)
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "postadd")
+            run([os.path.join(REF, "addprobe"), os.path.join(d, "index"),
+                 os.path.join(d, "add16_vectors.bin"), out])
+            before = read_default(os.path.join(d, "index", "graph.bin"), np.int32)
+            after = read_default(os.path.join(out, "graph.bin"), np.int32)
+            vec = read_default(os.path.join(out, "vectors.bin"), dtype)
+        n0, deg = before.shape
+        assert after.shape == (n0 + NADD_COSINE, deg) and vec.shape[0] == after.shape[0]
+        changed = np.where((after[:n0] != before).any(axis=1))[0]
+        rows = np.concatenate([changed, np.arange(n0, n0 + NADD_COSINE)]).astype(np.int32)
+        write_default(os.path.join(d, "postadd16_vectors.bin"), vec[n0:])
+        with open(os.path.join(d, "postadd16_rows.bin"), "wb") as f:
+            f.write(np.array([after.shape[0], deg, len(rows)], dtype=np.int32).tobytes())
+            f.write(np.column_stack([rows, after[rows]]).astype(np.int32).tobytes())
+        print(f"cosine add golden {name}: {len(changed)} old rows changed")
 
 
 def main():
@@ -220,4 +276,6 @@ def main():
 
 
 if __name__ == "__main__":
+    if sys.argv[1:] == ["cosine-add"]:
+        sys.exit(gen_cosine_add_goldens())
     sys.exit(main())

@@ -359,6 +359,12 @@ def build_kdt_tree(vectors, *, ntrees=1, sample_dims=16, seed=2016,
                 break
             if verbose and level % 8 == 0:
                 print(f"  kdt tree {t}: level {level}, {nseg} open segments")
+        if n == 1:
+            # a lone point never reaches a split, and a root left at zeros
+            # names itself as both children: the search would descend for
+            # ever. Leaf 0 on the left, the empty-side leaf on the right.
+            left_np[0] = -1
+            right_np[0] = -(np.int64(n) + 1)
         nodes = np.zeros((len(left_np), 4), dtype=np.int32)
         nodes[:, 0] = left_np + np.where(left_np >= 0, base, 0)
         nodes[:, 1] = right_np + np.where(right_np >= 0, base, 0)

@@ -592,6 +592,14 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
     if (const char* e = getenv("SPTAG_AMD_NG_CAP"))   /* perf experiments */
         cfg.ng_cap = std::max(256, atoi(e));
     cfg.spt_cap = 4096;
+    /* The reduced heaps emulate the reference's only while they are the
+     * smaller ones: a heap that is full at the reference's capacity
+     * (WorkSpace.h:265: 30*MaxCheck and 10*MaxCheck) replaces its largest
+     * last-level entry, one with room left just appends. Below MaxCheck 18
+     * (frontier) and 410 (tree heap) the sizes above are the larger ones,
+     * so they are cut to the reference's. */
+    cfg.ng_cap = std::min(cfg.ng_cap, max_check * 30);
+    cfg.spt_cap = std::min(cfg.spt_cap, max_check * 10);
     /* phase-cycle diagnostic (BKT kernels only — the KDT kernel writes
      * plain stride-2 stats) */
     cfg.prof = (getenv("SPTAG_AMD_PROF") && ix->algo == ALGO_BKT) ? 1 : 0;
@@ -837,6 +845,24 @@ int sptag_amd_iter_next(SptagAmdIterBatch* it, int32_t batch,
         return SPTAG_AMD_ERR_INTERNAL;
     }
     HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    /* The heaps sit at the reference's capacities, so a set overflow flag
+     * means the fixed visited table gave up probing (the reference's grows
+     * on demand and its iterator runs on past MaxCheck). The kernel has
+     * stopped that query early; its short count would read as exhaustion —
+     * a silent result truncation, so it is an error, as in the one-shot
+     * search. The flag is sticky: every later call fails the same way. */
+    std::vector<IterState> st(it->nq);
+    HIP_OR_FAIL(hipMemcpy(st.data(), ib.state, (size_t)it->nq * sizeof(IterState),
+                          hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
+    for (int32_t i = 0; i < it->nq; i++) {
+        if (st[i].oflow) {
+            fprintf(stderr,
+                    "sptag_amd: iterator query %d overflowed at reference "
+                    "capacities (visited-table saturation, %d slots); "
+                    "create the iterator with a larger MaxCheck\n", i, it->vcap);
+            return SPTAG_AMD_ERR_INTERNAL;
+        }
+    }
     HIP_OR_FAIL(hipMemcpy(out_vids, ib.out_vids, obytes, hipMemcpyDeviceToHost),
                 SPTAG_AMD_ERR_NOGPU);
     HIP_OR_FAIL(hipMemcpy(out_dists, ib.out_dists, obytes, hipMemcpyDeviceToHost),
