@@ -188,6 +188,91 @@ def gen_cosine_add_goldens():
         print(f"cosine add golden {name}: {len(changed)} old rows changed")
 
 
+# Distance pairs: every generic-form tail below 144, then the fixed-dim forms,
+# their neighbours and MAX_DIM; int8 up to 260, the largest admitted dim.
+DIST_DIMS_F32 = list(range(1, 145)) + [160, 192, 255, 256, 257, 384, 512, 513,
+                                       768, 1024, 4096]
+DIST_DIMS_I8 = list(range(1, 145)) + [160, 192, 255, 256, 257, 258, 259, 260]
+DIST_PPD = 3
+DIST_SEED_F32 = 20240
+DIST_SEED_I8 = 20241
+
+
+def dist_pairs_f32(dims=DIST_DIMS_F32, seed=DIST_SEED_F32):
+    """Per dim three (x, y) pairs: standard normal; magnitudes spread over
+    six decades, so that the fold order changes the rounded sum; both unit
+    length, the cosine case."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for d in dims:
+        p = rng.standard_normal((2, d))
+        s = rng.standard_normal((2, d)) * 10.0 ** rng.uniform(-3, 3, (2, d))
+        u = rng.standard_normal((2, d))
+        u = u.astype(np.float32)
+        u = u / np.linalg.norm(u.astype(np.float64), axis=1, keepdims=True)
+        out.append(np.stack([p, s, u]).astype(np.float32))   # [3, 2, d]
+    return out
+
+
+def dist_pairs_i8(dims=DIST_DIMS_I8, seed=DIST_SEED_I8):
+    """Per dim three pairs: uniform over the whole range; all -128 against
+    all 127, the largest distance there is; the same with the last 126."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for d in dims:
+        p = rng.integers(-128, 128, (2, d))
+        e = np.stack([np.full(d, -128), np.full(d, 127)])
+        f = e.copy()
+        f[1, -1] = 126
+        out.append(np.stack([p, e, f]).astype(np.int8))
+    return out
+
+
+def write_dist_pairs(path, vt, dims, pairs):
+    with open(path, "wb") as f:
+        f.write(np.array([vt, len(dims), DIST_PPD] + list(dims),
+                         dtype=np.int32).tobytes())
+        for a in pairs:
+            f.write(np.ascontiguousarray(a).tobytes())
+
+
+def gen_dist_goldens():
+    """The reference's own ComputeDistance on seeded pairs at every dim
+    form (distprobe). Plain files directly under tests/golden/:
+      dist_pairs_{f32,i8}.bin  the pairs, in distprobe's input format
+      dist_ref_{f32,i8}.bin    float32 [ndims * ppd][2]: L2, Cosine
+      dist_pairs.json          dims, pairs per dim, seeds, instruction set
+    Reachable on its own as `gen_golden.py dist`; no index is rebuilt."""
+    meta = {"pairs_per_dim": DIST_PPD, "metrics": ["L2", "Cosine"]}
+    isets = set()
+    for tag, vt, dims, seed, mk in [
+            ("f32", 0, DIST_DIMS_F32, DIST_SEED_F32, dist_pairs_f32),
+            ("i8", 1, DIST_DIMS_I8, DIST_SEED_I8, dist_pairs_i8)]:
+        src = os.path.join(GOLDEN, f"dist_pairs_{tag}.bin")
+        dst = os.path.join(GOLDEN, f"dist_ref_{tag}.bin")
+        write_dist_pairs(src, vt, dims, mk())
+        cmd = [os.path.join(REF, "distprobe"), src, dst]
+        print("+", " ".join(cmd))
+        out = subprocess.run(cmd, check=True, cwd=REPO, capture_output=True,
+                             text=True).stdout
+        iset = out.split("instruction_set", 1)[1].split()[0]
+        print(out.strip())
+        isets.add(iset)
+        assert os.path.getsize(dst) == len(dims) * DIST_PPD * 8
+        meta[tag] = {"dims": list(dims), "seed": seed}
+    # the oracle restates the AVX512 order; values of another path would pin
+    # the wrong thing
+    if isets != {"AVX512"}:
+        for tag in ("f32", "i8"):
+            os.remove(os.path.join(GOLDEN, f"dist_ref_{tag}.bin"))
+            os.remove(os.path.join(GOLDEN, f"dist_pairs_{tag}.bin"))
+        sys.exit(f"reference took {sorted(isets)}, not AVX512: no fixture written")
+    meta["instruction_set"] = "AVX512"
+    with open(os.path.join(GOLDEN, "dist_pairs.json"), "w") as f:
+        json.dump(meta, f)
+    print("distance pairs done")
+
+
 def main():
     os.makedirs(GOLDEN, exist_ok=True)
     rng = np.random.default_rng(2016)
@@ -278,4 +363,6 @@ def main():
 if __name__ == "__main__":
     if sys.argv[1:] == ["cosine-add"]:
         sys.exit(gen_cosine_add_goldens())
+    if sys.argv[1:] == ["dist"]:
+        sys.exit(gen_dist_goldens())
     sys.exit(main())

@@ -652,6 +652,8 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
 
     int32_t gq_n = all_global ? nq : (int32_t)redo.size();
     if (gq_n == 0) return SPTAG_AMD_OK;
+    if (getenv("SPTAG_AMD_DEBUG"))
+        fprintf(stderr, "sptag_amd: global-heap pass for %d/%d queries\n", gq_n, nq);
     SearchCfg c2 = cfg;
     c2.nq = gq_n;
     c2.ng_cap = max_check * 30;     /* reference capacities */

@@ -346,7 +346,10 @@ DEV float ref_dist_grp_f32(const float* __restrict__ q,
 }
 
 /* int8: exact integer accumulation (order-free; partials exact in the
- * reference's float lanes for dim*254^2 < 2^24 — guarded host-side).
+ * reference's float lanes for dim*254^2 < 2^24 — guarded host-side:
+ * create_index() in host.cpp, which every create and load entry point goes
+ * through, refuses int8 dims of 261 and more;
+ * tests/test_abi.py::test_create_validation exercises it).
  * The dword path runs on the CDNA4 int8 dot units (v_dot4c_i32_i8 via
  * __builtin_amdgcn_sdot4) — the gfx950 analog of the reference's own GPU
  * __dp4a int8 path (cuda/Distance.hxx:84-101). Integer dots are exact and

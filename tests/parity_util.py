@@ -91,24 +91,74 @@ def orc_vectors(oix):
 
 
 # ---------------------------------------------------------------------------
+# distance pairs recorded from the reference's own ComputeDistance
+# ---------------------------------------------------------------------------
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_dist_pairs = {}
+
+
+def load_dist_pairs(tag):
+    """The committed pairs of `tag` ("f32" or "i8") and what the reference
+    computed on them (oracle/gen_golden.py dist): (dims, pairs, ref), where
+    pairs[i] is [ppd, 2, dims[i]] (x then y) and ref is float32
+    [ndims, ppd, 2] (L2, Cosine). Read once, read-only."""
+    if tag not in _dist_pairs:
+        dtype = np.float32 if tag == "f32" else np.int8
+        raw = open(os.path.join(GOLDEN, f"dist_pairs_{tag}.bin"), "rb").read()
+        vt, ndims, ppd = np.frombuffer(raw, dtype=np.int32, count=3)
+        assert vt == (0 if tag == "f32" else 1)
+        dims = np.frombuffer(raw, dtype=np.int32, count=ndims, offset=12).tolist()
+        esz = np.dtype(dtype).itemsize
+        off, pairs = 12 + 4 * ndims, []
+        for d in dims:
+            a = np.frombuffer(raw, dtype=dtype, count=ppd * 2 * d, offset=off)
+            pairs.append(a.reshape(ppd, 2, d))
+            off += ppd * 2 * d * esz
+        assert off == len(raw)
+        ref = np.fromfile(os.path.join(GOLDEN, f"dist_ref_{tag}.bin"),
+                          dtype=np.float32).reshape(ndims, ppd, 2)
+        ref.setflags(write=False)
+        _dist_pairs[tag] = (dims, pairs, ref)
+    return _dist_pairs[tag]
+
+
+# ---------------------------------------------------------------------------
 # seeded CPU-built indexes
 # ---------------------------------------------------------------------------
 
 _built = {}
 
 
-def built_case(n, dim, vt, dm, algo="BKT", nq=8):
+def built_case(n, dim, vt, dm, algo="BKT", nq=8, seed=0, latent=0):
     """Seeded random index built on the CPU, with queries. Cached per
-    (n, dim, vt, dm, algo); callers must not modify what they get."""
-    key = (n, dim, vt, dm, algo)
+    argument tuple; callers must not modify what they get.
+
+    With latent = 0 every element is independent. At dims of 60 and more
+    such points are all nearly equally far apart, and no graph search
+    finds the nearest one within a small MaxCheck. latent = m draws rows
+    and queries as m standard-normal factors times a random [m, dim]
+    matrix, plus 5% independent noise: full-rank data that a search can
+    find its way through."""
+    key = (n, dim, vt, dm, algo, nq, seed, latent)
     if key not in _built:
         from sptag_amd.build import build_index_arrays
-        rng = np.random.default_rng(7000 + 31 * n + dim + (0 if vt == "f32" else 1))
+        rng = np.random.default_rng(7000 + 31 * n + dim + (0 if vt == "f32" else 1)
+                                    + 100003 * seed)
+        if latent:
+            mix = rng.standard_normal((latent, dim)) / np.sqrt(latent)
+            draw = lambda m: (rng.standard_normal((m, latent)) @ mix
+                              + 0.05 * rng.standard_normal((m, dim)))
+        else:
+            draw = lambda m: rng.standard_normal((m, dim))
         if vt == "f32":
-            x = rng.standard_normal((n, dim)).astype(np.float32)
-            q = rng.standard_normal((nq, dim)).astype(np.float32)
+            x = draw(n).astype(np.float32)
+            q = draw(nq).astype(np.float32)
             if dm == "Cosine":
                 q = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+        elif latent:
+            x = np.clip(np.rint(draw(n) * 40), -100, 100).astype(np.int8)
+            q = np.clip(np.rint(draw(nq) * 40), -100, 100).astype(np.int8)
         else:
             x = rng.integers(-100, 101, (n, dim)).astype(np.int8)
             q = rng.integers(-100, 101, (nq, dim)).astype(np.int8)
