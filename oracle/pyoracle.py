@@ -72,48 +72,40 @@ class OrcIndex:
         return cls(load_library().orc_load_index(str(folder).encode()))
 
     @classmethod
-    def from_arrays(cls, vectors, tree_start, tree_nodes, graph, distmethod,
-                    deleted=None):
+    def _from_arrays(cls, symbol, words, vectors, tree_start, nodes, graph,
+                     distmethod, deleted):
+        """`symbol` names the C constructor, `words` is the int32 count of
+        one tree node (BKT 3, KDT 4)."""
         lib = load_library()
         vectors = np.ascontiguousarray(vectors)
         vt = 0 if vectors.dtype == np.float32 else 1
         dm = {"L2": 0, "Cosine": 1}.get(distmethod, distmethod)
         tree_start = np.ascontiguousarray(tree_start, dtype=np.int32)
-        tree_nodes = np.ascontiguousarray(tree_nodes, dtype=np.int32)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
         graph = np.ascontiguousarray(graph, dtype=np.int32)
         delp = None
         if deleted is not None:
             deleted = np.ascontiguousarray(deleted, dtype=np.uint8)
             delp = deleted.ctypes.data_as(ctypes.c_void_p)
-        h = lib.orc_create_index(
+        h = getattr(lib, symbol)(
             vectors.shape[0], vectors.shape[1], vt, dm,
             vectors.ctypes.data_as(ctypes.c_void_p),
             len(tree_start), tree_start.ctypes.data_as(ctypes.c_void_p),
-            tree_nodes.size // 3, tree_nodes.ctypes.data_as(ctypes.c_void_p),
+            nodes.size // words, nodes.ctypes.data_as(ctypes.c_void_p),
             graph.shape[1], graph.ctypes.data_as(ctypes.c_void_p), delp)
         return cls(h)
 
     @classmethod
+    def from_arrays(cls, vectors, tree_start, tree_nodes, graph, distmethod,
+                    deleted=None):
+        return cls._from_arrays("orc_create_index", 3, vectors, tree_start,
+                                tree_nodes, graph, distmethod, deleted)
+
+    @classmethod
     def from_arrays_kdt(cls, vectors, tree_start, kdt_nodes, graph, distmethod,
                         deleted=None):
-        lib = load_library()
-        vectors = np.ascontiguousarray(vectors)
-        vt = 0 if vectors.dtype == np.float32 else 1
-        dm = {"L2": 0, "Cosine": 1}.get(distmethod, distmethod)
-        tree_start = np.ascontiguousarray(tree_start, dtype=np.int32)
-        kdt_nodes = np.ascontiguousarray(kdt_nodes, dtype=np.int32)
-        graph = np.ascontiguousarray(graph, dtype=np.int32)
-        delp = None
-        if deleted is not None:
-            deleted = np.ascontiguousarray(deleted, dtype=np.uint8)
-            delp = deleted.ctypes.data_as(ctypes.c_void_p)
-        h = lib.orc_create_kdt_index(
-            vectors.shape[0], vectors.shape[1], vt, dm,
-            vectors.ctypes.data_as(ctypes.c_void_p),
-            len(tree_start), tree_start.ctypes.data_as(ctypes.c_void_p),
-            kdt_nodes.size // 4, kdt_nodes.ctypes.data_as(ctypes.c_void_p),
-            graph.shape[1], graph.ctypes.data_as(ctypes.c_void_p), delp)
-        return cls(h)
+        return cls._from_arrays("orc_create_kdt_index", 4, vectors, tree_start,
+                                kdt_nodes, graph, distmethod, deleted)
 
     def __del__(self):
         if getattr(self, "_h", None):

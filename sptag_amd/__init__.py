@@ -142,55 +142,48 @@ class AnnIndex:
         return ix
 
     @classmethod
-    def FromArrays(cls, vectors, tree_start, tree_nodes, graph, distmethod,
-                   deleted=None, device=0):
-        """Assemble from raw numpy blobs (file layouts without headers)."""
-        lib = load_library()
+    def _from_arrays(cls, symbol, words, vectors, tree_start, nodes, graph,
+                     distmethod, deleted, device):
+        """Shared body of FromArrays / FromArraysKDT: `symbol` names the C
+        constructor, `words` is the int32 count of one tree node."""
         vectors = np.ascontiguousarray(vectors)
-        vt = VT_FLOAT if vectors.dtype == np.float32 else VT_INT8
         if vectors.dtype not in (np.float32, np.int8):
             raise ValueError("dtype must be float32 or int8")
+        lib = load_library()
+        vt = VT_FLOAT if vectors.dtype == np.float32 else VT_INT8
         n, dim = vectors.shape
         tree_start = np.ascontiguousarray(tree_start, dtype=np.int32)
-        tree_nodes = np.ascontiguousarray(tree_nodes, dtype=np.int32)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
         graph = np.ascontiguousarray(graph, dtype=np.int32)
         dm = {"L2": DM_L2, "Cosine": DM_COSINE}.get(distmethod, distmethod)
         delp = None
         if deleted is not None:
             deleted = np.ascontiguousarray(deleted, dtype=np.uint8)
             delp = deleted.ctypes.data_as(ctypes.c_void_p)
-        h = lib.sptag_amd_create_index(
+        h = getattr(lib, symbol)(
             n, dim, vt, dm, vectors.ctypes.data_as(ctypes.c_void_p),
             len(tree_start), tree_start.ctypes.data_as(ctypes.c_void_p),
-            tree_nodes.size // 3, tree_nodes.ctypes.data_as(ctypes.c_void_p),
+            nodes.size // words, nodes.ctypes.data_as(ctypes.c_void_p),
             graph.shape[1], graph.ctypes.data_as(ctypes.c_void_p),
             delp, device)
         return cls(h)
+
+    @classmethod
+    def FromArrays(cls, vectors, tree_start, tree_nodes, graph, distmethod,
+                   deleted=None, device=0):
+        """Assemble from raw numpy blobs (file layouts without headers)."""
+        return cls._from_arrays("sptag_amd_create_index", 3, vectors,
+                                tree_start, tree_nodes, graph, distmethod,
+                                deleted, device)
 
     @classmethod
     def FromArraysKDT(cls, vectors, tree_start, kdt_nodes, graph, distmethod,
                       deleted=None, device=0):
         """KDT variant: kdt_nodes is an int32 [N,4] array whose 4th column
         holds the float split_value bit pattern (KDTree.h:22)."""
-        lib = load_library()
-        vectors = np.ascontiguousarray(vectors)
-        vt = VT_FLOAT if vectors.dtype == np.float32 else VT_INT8
-        n, dim = vectors.shape
-        tree_start = np.ascontiguousarray(tree_start, dtype=np.int32)
-        kdt_nodes = np.ascontiguousarray(kdt_nodes, dtype=np.int32)
-        graph = np.ascontiguousarray(graph, dtype=np.int32)
-        dm = {"L2": DM_L2, "Cosine": DM_COSINE}.get(distmethod, distmethod)
-        delp = None
-        if deleted is not None:
-            deleted = np.ascontiguousarray(deleted, dtype=np.uint8)
-            delp = deleted.ctypes.data_as(ctypes.c_void_p)
-        h = lib.sptag_amd_create_index_kdt(
-            n, dim, vt, dm, vectors.ctypes.data_as(ctypes.c_void_p),
-            len(tree_start), tree_start.ctypes.data_as(ctypes.c_void_p),
-            kdt_nodes.size // 4, kdt_nodes.ctypes.data_as(ctypes.c_void_p),
-            graph.shape[1], graph.ctypes.data_as(ctypes.c_void_p),
-            delp, device)
-        return cls(h)
+        return cls._from_arrays("sptag_amd_create_index_kdt", 4, vectors,
+                                tree_start, kdt_nodes, graph, distmethod,
+                                deleted, device)
 
     def __del__(self):
         if getattr(self, "_owns", False) and getattr(self, "_h", None):
@@ -228,15 +221,22 @@ class AnnIndex:
         return self._lib.sptag_amd_default_maxcheck(self._h)
 
     # -- search -------------------------------------------------------
+    def _rows(self, a):
+        """`a` as the C side reads row vectors: contiguous, the index's
+        dtype, [rows, dim] (a single vector becomes one row)."""
+        a = np.ascontiguousarray(a, dtype=_np_dtype(self.valuetype))
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError(f"expected rows of {self.dim} values, got shape {a.shape}")
+        return a
+
     def BatchSearch(self, queries, k, max_check=0):
         """GPU batched search. Returns (vids int32 [nq,k], dists f32 [nq,k]),
         ascending by (dist, vid), vid=-1 padding — the contract of the
         reference batch overload VectorIndex.h:103."""
-        queries = np.ascontiguousarray(queries, dtype=_np_dtype(self.valuetype))
-        if queries.ndim == 1:
-            queries = queries[None, :]
+        queries = self._rows(queries)
         nq = queries.shape[0]
-        assert queries.shape[1] == self.dim, (queries.shape, self.dim)
         vids = np.empty((nq, k), dtype=np.int32)
         dists = np.empty((nq, k), dtype=np.float32)
         rc = self._lib.sptag_amd_search_batch(
@@ -281,9 +281,7 @@ class AnnIndex:
 
     def Truth(self, queries, k):
         """Exact brute-force top-k on the GPU."""
-        queries = np.ascontiguousarray(queries, dtype=_np_dtype(self.valuetype))
-        if queries.ndim == 1:
-            queries = queries[None, :]
+        queries = self._rows(queries)
         nq = queries.shape[0]
         vids = np.empty((nq, k), dtype=np.int32)
         dists = np.empty((nq, k), dtype=np.float32)
@@ -298,10 +296,7 @@ class AnnIndex:
     def Add(self, vectors, normalized=False):
         """Online add (reference AddIndex semantics below the tree-rebuild
         threshold); runs GPU refine searches per added vector."""
-        vectors = np.ascontiguousarray(vectors,
-                                       dtype=_np_dtype(self.valuetype))
-        if vectors.ndim == 1:
-            vectors = vectors[None, :]
+        vectors = self._rows(vectors)
         rc = self._lib.sptag_amd_add(
             self._h, vectors.ctypes.data_as(ctypes.c_void_p),
             vectors.shape[0], 1 if normalized else 0)
@@ -320,10 +315,7 @@ class AnnIndex:
     def DeleteByVector(self, vectors):
         """Delete exact duplicates of the given vectors (reference
         DeleteIndex(const void*, n) semantics: CEF search + dist < 1e-6)."""
-        vectors = np.ascontiguousarray(vectors,
-                                       dtype=_np_dtype(self.valuetype))
-        if vectors.ndim == 1:
-            vectors = vectors[None, :]
+        vectors = self._rows(vectors)
         rc = self._lib.sptag_amd_delete_by_vector(
             self._h, vectors.ctypes.data_as(ctypes.c_void_p), vectors.shape[0])
         if rc != 0:
@@ -403,10 +395,7 @@ class IterBatch:
     def __init__(self, index, queries, max_check=0):
         self._lib = index._lib
         self._index = index   # keep the index alive
-        queries = np.ascontiguousarray(queries,
-                                       dtype=_np_dtype(index.valuetype))
-        if queries.ndim == 1:
-            queries = queries[None, :]
+        queries = index._rows(queries)
         self.nq = queries.shape[0]
         self._h = self._lib.sptag_amd_iter_create(
             index._h, queries.ctypes.data_as(ctypes.c_void_p), self.nq,

@@ -7,8 +7,9 @@ Mirrors the reference build SEMANTICS (citations to /root/reference/AnnService):
   - BKT: hierarchical k-means tree, node children contiguous, leaf nodes are
     the vectors themselves, node centerid is a member vector
     (BKTree.h:547-625). Build is not deterministic in the reference either
-    (std::mt19937 shuffles — SURVEY.md §8c), so equivalence is judged by
-    search recall/QPS on the produced index, not bytes.
+    (std::mt19937 shuffles — SURVEY.md §8c), so equivalence WITH THE
+    REFERENCE is judged by search recall/QPS on the produced index; an edit
+    of this file is judged on bytes against its parent.
   - KNN graph: TP-tree partitions, exact KNN inside each leaf, candidates
     merged over trees (NeighborhoodGraph.h:301-360);
   - RNG prune: candidates ascending by distance, accept c iff for every
@@ -40,20 +41,60 @@ def normalize_base(vectors, distmethod):
 
 
 # ------------------------------------------------------------------ #
+# steps shared by the tree and graph builders
+# ------------------------------------------------------------------ #
+
+def _prologue(vectors, device, seed):
+    """(device, float32 view of `vectors` on it, Generator seeded `seed`)."""
+    device = device or _dev()
+    xf = torch.as_tensor(vectors, device=device)
+    if xf.dtype != torch.float32:
+        xf = xf.float()
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    return device, xf, gen
+
+
+def _chunks(n, c):
+    """(start, end) of consecutive row chunks of at most c rows."""
+    for s in range(0, n, c):
+        yield s, min(n, s + c)
+
+
+def _segmented_order(key, seg, stable=False):
+    """Permutation that groups elements by segment id (ascending, earlier
+    order kept) and sorts each segment by key. `stable` is the FIRST sort's
+    flag: it decides the order of equal keys, and so the index."""
+    o1 = key.argsort(stable=stable)
+    return o1[seg[o1].argsort(stable=True)]
+
+
+def _seg_starts(counts):
+    """Exclusive prefix sum of segment sizes (numpy array or tensor)."""
+    return counts.cumsum(0) - counts
+
+
+def _pos_in_segment(seg, counts):
+    """Rank of each element inside its segment; `seg` holds contiguous
+    ascending segment ids, `counts` the segment sizes."""
+    return (torch.arange(seg.numel(), device=seg.device)
+            - _seg_starts(counts)[seg])
+
+
+def _pairwise_sq_l2(pts):
+    """[B, m, d] -> [B, m, m] squared L2 between the rows of each batch."""
+    sq = (pts * pts).sum(-1)
+    return sq[:, :, None] + sq[:, None, :] - 2.0 * torch.bmm(pts, pts.transpose(1, 2))
+
+
+# ------------------------------------------------------------------ #
 # BKT tree
 # ------------------------------------------------------------------ #
 
 def _ragged_arange(counts):
-    """[0..c0), [0..c1), ... concatenated (numpy)."""
+    """[0..c0), [0..c1), ... concatenated (numpy); zero counts allowed."""
     counts = np.asarray(counts, dtype=np.int64)
-    total = int(counts.sum())
-    if total == 0:
-        return np.zeros(0, dtype=np.int64)
-    out = np.ones(total, dtype=np.int64)
-    out[0] = 0
-    starts = np.cumsum(counts)[:-1]
-    out[starts] = 1 - counts[:-1]
-    return np.cumsum(out)
+    return np.arange(counts.sum()) - np.repeat(_seg_starts(counts), counts)
 
 
 def _kmeans_split(xf, members, K, iters=8, sample=4096, gen=None):
@@ -113,13 +154,8 @@ def build_bkt_tree(vectors, *, kmeans_k=32, leaf_size=32, big_cluster=4096,
     """Returns (tree_start int32[ntrees], tree_nodes int32[N,3]) in the
     reference layout (BKTree.h:25 BKTNode {centerid,childStart,childEnd},
     children contiguous, childEnd exclusive, leaves childStart=-1)."""
-    device = device or _dev()
-    n = vectors.shape[0]
-    xf = torch.as_tensor(vectors, device=device)
-    if xf.dtype != torch.float32:
-        xf = xf.float()
-    gen = torch.Generator(device=device)
-    gen.manual_seed(seed)
+    device, xf, gen = _prologue(vectors, device, seed)
+    n = xf.shape[0]
 
     cent, cs, ce = [n], [-1], [-1]   # root: centerid=n (unused; as reference)
     small = []                        # (node_idx, members) clusters <= big_cluster
@@ -147,75 +183,51 @@ def build_bkt_tree(vectors, *, kmeans_k=32, leaf_size=32, big_cluster=4096,
 
     # vectorized bottom: each small cluster -> groups of <= leaf_size members
     # (ordered by distance to the cluster centroid), each group an internal
-    # node whose children are member leaves. Fully vectorized (no per-cluster
-    # python loop) so 100M-scale builds stay fast.
+    # node whose children are member leaves; a cluster of <= leaf_size
+    # members has no group level. Fully vectorized (no per-cluster python
+    # loop) so 100M-scale builds stay fast.
     if small:
         nbase = len(cent)
-        dev = xf.device
+        node_np = np.array([nd for nd, _ in small])
         members_all = torch.cat([g for _, g in small])
+        sizes_t = torch.tensor([g.numel() for _, g in small], device=device)
         cl_of = torch.repeat_interleave(
-            torch.arange(len(small), device=dev),
-            torch.tensor([g.numel() for _, g in small], device=dev))
-        ncl = len(small)
-        sizes_t = torch.tensor([g.numel() for _, g in small], device=dev)
+            torch.arange(len(small), device=device), sizes_t)
         # order members within each cluster by distance to its centroid
         pts = xf[members_all]
-        cen = torch.zeros((ncl, pts.shape[1]), device=dev)
+        cen = torch.zeros((len(small), pts.shape[1]), device=device)
         cen.index_add_(0, cl_of, pts)
         cen = cen / sizes_t[:, None].float()
         dcent = ((pts - cen[cl_of]) ** 2).sum(1)
-        o1 = dcent.argsort()
-        o2 = cl_of[o1].argsort(stable=True)
-        order = o1[o2]
-        members_all = members_all[order]          # cluster-major, dist-ordered
-        mem_np = members_all.cpu().numpy()
+        # cluster-major, dist-ordered
+        mem_np = members_all[_segmented_order(dcent, cl_of)].cpu().numpy()
         sizes = sizes_t.cpu().numpy()
-        node_np = np.array([nd for nd, _ in small])
 
-        gcnts = np.ceil(sizes / leaf_size).astype(np.int64)
-        has_groups = sizes > leaf_size
-        n_group_nodes = np.where(has_groups, gcnts, 0)
-        extra = n_group_nodes + sizes              # nodes per cluster
-        offs = nbase + np.concatenate([[0], np.cumsum(extra)[:-1]])
+        # a cluster's block: its group nodes (none if it fits one leaf
+        # group), then its members as leaves, leaf_size-packed per group
+        ngroups = np.where(sizes > leaf_size,
+                           np.ceil(sizes / leaf_size).astype(np.int64), 0)
+        extra = ngroups + sizes                    # nodes per cluster
+        offs = nbase + _seg_starts(extra)
+        mstart = _seg_starts(sizes)
+        cs[node_np] = offs
+        ce[node_np] = offs + np.where(ngroups > 0, ngroups, sizes)
         total = int(extra.sum())
         cent2 = np.empty(total, dtype=np.int64)
         cs2 = np.full(total, -1, dtype=np.int64)
         ce2 = np.full(total, -1, dtype=np.int64)
-
-        mstart = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-        # clusters WITHOUT group level: children = member leaves
-        nog = ~has_groups
-        cs[node_np[nog]] = offs[nog]
-        ce[node_np[nog]] = offs[nog] + sizes[nog]
-        # their leaf slots: positions offs..offs+size-1 (local p = offs-nbase)
-        if nog.any():
-            lp = offs[nog] - nbase
-            idx = np.repeat(lp, sizes[nog]) + _ragged_arange(sizes[nog])
-            src = mem_np[np.repeat(mstart[nog], sizes[nog]) + _ragged_arange(sizes[nog])]
-            cent2[idx] = src
-        # clusters WITH a group level
-        wg = has_groups
-        if wg.any():
-            cs[node_np[wg]] = offs[wg]
-            ce[node_np[wg]] = offs[wg] + gcnts[wg]
-            gtot = int(gcnts[wg].sum())
-            # per group: cluster idx, group idx within cluster
-            gcl = np.repeat(np.where(wg)[0], gcnts[wg])
-            ggi = _ragged_arange(gcnts[wg])
-            gsz = np.minimum(leaf_size, sizes[gcl] - ggi * leaf_size)
-            # leaf block offsets: per cluster leaves start at offs+gcnt
-            leaf_base = offs[gcl] + gcnts[gcl] + ggi * leaf_size
-            # careful: groups are leaf_size-packed so cumulative offset works
-            gmemstart = mstart[gcl] + ggi * leaf_size
-            gpos = offs[gcl] - nbase + ggi        # group node local position
-            cent2[gpos] = mem_np[gmemstart]
-            cs2[gpos] = leaf_base
-            ce2[gpos] = leaf_base + gsz
-            # leaves
-            lidx = np.repeat(leaf_base - nbase, gsz) + _ragged_arange(gsz)
-            lsrc = mem_np[np.repeat(gmemstart, gsz) + _ragged_arange(gsz)]
-            cent2[lidx] = lsrc
-            del gtot
+        # leaves
+        cent2[np.repeat(offs - nbase + ngroups, sizes)
+              + _ragged_arange(sizes)] = mem_np
+        # per group: cluster idx, group idx within cluster
+        gcl = np.repeat(np.arange(len(small)), ngroups)
+        ggi = _ragged_arange(ngroups)
+        gsz = np.minimum(leaf_size, sizes[gcl] - ggi * leaf_size)
+        leaf_base = offs[gcl] + ngroups[gcl] + ggi * leaf_size
+        gpos = offs[gcl] - nbase + ggi             # group node local position
+        cent2[gpos] = mem_np[mstart[gcl] + ggi * leaf_size]
+        cs2[gpos] = leaf_base
+        ce2[gpos] = leaf_base + gsz
         cent = np.concatenate([cent, cent2])
         cs = np.concatenate([cs, cs2])
         ce = np.concatenate([ce, ce2])
@@ -235,6 +247,56 @@ def build_bkt_tree(vectors, *, kmeans_k=32, leaf_size=32, big_cluster=4096,
 # split on a high-variance dim at the mean; leaves encode -(vecid+1))
 # ------------------------------------------------------------------ #
 
+def _kdt_split(xf, perm, seg, cnt, sample_dims, gen):
+    """Split every open segment of one level at once: dimension of largest
+    variance among a random subset, at the segment mean. `perm` lists the
+    open members segment by segment, `seg` their segment ids, `cnt` the
+    segment sizes. Returns (perm reordered to left-then-right inside each
+    segment, side of each member in that order, left counts, split dims,
+    split values)."""
+    nseg, d = cnt.numel(), xf.shape[1]
+    dims = torch.randperm(d, generator=gen, device=xf.device)[:min(sample_dims, d)]
+    xs = xf[perm][:, dims]                       # [n, k16]
+    sums = torch.zeros(nseg, dims.numel(), device=xf.device).index_add_(0, seg, xs)
+    sqs = torch.zeros(nseg, dims.numel(), device=xf.device).index_add_(0, seg, xs * xs)
+    cf = cnt.float().clamp(min=1)[:, None]
+    var = sqs / cf - (sums / cf) ** 2
+    sd_local = var.argmax(1)                     # [nseg]
+    split_val = sums.gather(1, sd_local[:, None]).squeeze(1) / cf.squeeze(1)
+    val_e = xs.gather(1, sd_local[seg][:, None]).squeeze(1)
+    side = val_e >= split_val[seg]               # right side (diff >= 0)
+    # guard degenerate splits (all equal): rank-split those segments
+    lcnt = torch.bincount(seg[~side], minlength=nseg)
+    bad = ((lcnt == 0) | (lcnt == cnt)) & (cnt >= 2)
+    if bool(bad.any()):
+        rank_side = _pos_in_segment(seg, cnt) >= (cnt[seg] // 2)
+        side = torch.where(bad[seg], rank_side, side)
+        lcnt = torch.bincount(seg[~side], minlength=nseg)
+    # order members: (seg, side) stable
+    order = _segmented_order(side.long(), seg, stable=True)
+    return perm[order], side[order], lcnt, dims[sd_local], split_val
+
+
+def _kdt_children(cnt, lcnt, perm, next_idx, n):
+    """Child links of one level's segments, as [2, nseg] arrays (row 0 left,
+    row 1 right). A side with >= 2 members becomes an internal node and gets
+    the next free node index — all left children of the level first, then
+    all right ones; a single member is the leaf -(id+1); an empty side is
+    the out-of-range leaf -(n+1), which the search ignores. Returns (child
+    links, new node index per side or -1). Only segments with cnt >= 2 are
+    internal; the rows of the others mean nothing."""
+    side_cnt = np.stack([lcnt, cnt - lcnt])
+    internal = side_cnt >= 2
+    new_ids = np.where(
+        internal, next_idx + np.cumsum(internal).reshape(internal.shape) - 1, -1)
+    child = np.where(internal, new_ids, -(np.int64(n) + 1))
+    leaf = (cnt >= 2) & (side_cnt == 1)
+    starts = _seg_starts(cnt)
+    first = np.stack([starts, starts + lcnt])     # first member of each side
+    child[leaf] = -(perm[first[leaf]] + 1)
+    return child, new_ids
+
+
 def build_kdt_tree(vectors, *, ntrees=1, sample_dims=16, seed=2016,
                    device=None, max_levels=64, verbose=False):
     """Level-vectorized kd-tree build. Returns (tree_start int32[ntrees],
@@ -242,13 +304,8 @@ def build_kdt_tree(vectors, *, ntrees=1, sample_dims=16, seed=2016,
     pattern (KDTNode layout, KDTree.h:22). Split dim = max-variance among a
     per-level random dim subset (reference: top-5 variance dims on a
     sample); split value = segment mean."""
-    device = device or _dev()
-    n, d = vectors.shape
-    xf = torch.as_tensor(vectors, device=device)
-    if xf.dtype != torch.float32:
-        xf = xf.float()
-    gen = torch.Generator(device=device)
-    gen.manual_seed(seed + 31)
+    device, xf, gen = _prologue(vectors, device, seed + 31)
+    n = xf.shape[0]
 
     tree_start = []
     all_nodes = []
@@ -256,10 +313,9 @@ def build_kdt_tree(vectors, *, ntrees=1, sample_dims=16, seed=2016,
     for t in range(ntrees):
         tree_start.append(base)
         # node storage (numpy, grown per level)
-        left_np = np.zeros(1, dtype=np.int64)
-        right_np = np.zeros(1, dtype=np.int64)
-        sdim_np_all = np.zeros(1, dtype=np.int64)
-        sval_np_all = np.zeros(1, dtype=np.float64)
+        kids = np.zeros((1, 2), dtype=np.int64)      # left, right
+        sdim = np.zeros(1, dtype=np.int64)
+        sval = np.zeros(1, dtype=np.float64)
         perm = torch.randperm(n, generator=gen, device=device)
         seg = torch.zeros(n, dtype=torch.int64, device=device)
         seg_node = np.array([0], dtype=np.int64)   # node idx per segment
@@ -268,93 +324,31 @@ def build_kdt_tree(vectors, *, ntrees=1, sample_dims=16, seed=2016,
             cnt = torch.bincount(seg, minlength=nseg)
             if int(cnt.max()) <= 1:
                 break
-            k16 = min(sample_dims, d)
-            dims = torch.randperm(d, generator=gen, device=device)[:k16]
-            xs = xf[perm][:, dims]                       # [n, k16]
-            sums = torch.zeros(nseg, k16, device=device).index_add_(0, seg, xs)
-            sqs = torch.zeros(nseg, k16, device=device).index_add_(0, seg, xs * xs)
-            cf = cnt.float().clamp(min=1)[:, None]
-            var = sqs / cf - (sums / cf) ** 2
-            sd_local = var.argmax(1)                     # [nseg]
-            split_dim = dims[sd_local]
-            split_val = sums.gather(1, sd_local[:, None]).squeeze(1) / cf.squeeze(1)
-            val_e = xs.gather(1, sd_local[seg][:, None]).squeeze(1)
-            side = val_e >= split_val[seg]               # right side (diff >= 0)
-            # guard degenerate splits (all equal): rank-split those segments
-            lcnt = torch.bincount(seg[~side], minlength=nseg)
-            rcnt = cnt - lcnt
-            bad = ((lcnt == 0) | (rcnt == 0)) & (cnt >= 2)
-            if bool(bad.any()):
-                starts = torch.cumsum(cnt, 0) - cnt
-                pos = torch.arange(n, device=device) - starts[seg]
-                rank_side = pos >= (cnt[seg] // 2)
-                side = torch.where(bad[seg], rank_side, side)
-                lcnt = torch.bincount(seg[~side], minlength=nseg)
-                rcnt = cnt - lcnt
-            # order members: (seg, side) stable
-            o1 = side.long().argsort(stable=True)
-            o2 = seg[o1].argsort(stable=True)
-            order = o1[o2]
-            perm = perm[order]
-            side = side[order]
-            # record this level's nodes (only segments with cnt >= 2 are
-            # internal; they were allocated a node idx in seg_node)
+            perm, side, lcnt, split_dim, split_val = _kdt_split(
+                xf, perm, seg, cnt, sample_dims, gen)
             cnt_np = cnt.cpu().numpy()
-            l_np = lcnt.cpu().numpy()
-            r_np = rcnt.cpu().numpy()
-            sd_np = split_dim.cpu().numpy()
-            sv_np = split_val.cpu().numpy()
-            starts_np = np.concatenate([[0], np.cumsum(cnt_np)[:-1]])
-            perm_np = perm.cpu().numpy()
-            # children allocation
-            internal = cnt_np >= 2
-            child_internal_l = internal & (l_np >= 2)
-            child_internal_r = internal & (r_np >= 2)
-            n_new = int(child_internal_l.sum() + child_internal_r.sum())
-            next_idx = len(left_np)
-            new_ids_l = np.full(nseg, -1, dtype=np.int64)
-            new_ids_r = np.full(nseg, -1, dtype=np.int64)
-            alloc = np.cumsum(np.concatenate(
-                [child_internal_l.astype(np.int64), child_internal_r.astype(np.int64)]))
-            new_ids_l[child_internal_l] = next_idx + alloc[:nseg][child_internal_l] - 1
-            new_ids_r[child_internal_r] = next_idx + alloc[nseg:][child_internal_r] - 1
-            left_np = np.concatenate([left_np, np.zeros(n_new, dtype=np.int64)])
-            right_np = np.concatenate([right_np, np.zeros(n_new, dtype=np.int64)])
-            sdim_np_all = np.concatenate([sdim_np_all, np.zeros(n_new, dtype=np.int64)])
-            sval_np_all = np.concatenate([sval_np_all, np.zeros(n_new)])
-            # children: internal -> allocated idx, single member -> -(id+1),
-            # empty side -> out-of-range leaf (ignored by search)
-            lchild = np.full(nseg, -(np.int64(n) + 1), dtype=np.int64)
-            rchild = np.full(nseg, -(np.int64(n) + 1), dtype=np.int64)
-            lchild[child_internal_l] = new_ids_l[child_internal_l]
-            rchild[child_internal_r] = new_ids_r[child_internal_r]
-            leaf_l = internal & (l_np == 1)
-            leaf_r = internal & (r_np == 1)
-            lchild[leaf_l] = -(perm_np[starts_np[leaf_l]] + 1)
-            rchild[leaf_r] = -(perm_np[starts_np[leaf_r] + l_np[leaf_r]] + 1)
-            li = np.where(internal)[0]
+            child, new_ids = _kdt_children(
+                cnt_np, lcnt.cpu().numpy(), perm.cpu().numpy(), len(kids), n)
+            # record this level's nodes (the internal segments were
+            # allocated a node idx in seg_node) and make room for the next
+            li = np.where(cnt_np >= 2)[0]
             tgt = seg_node[li]
-            left_np[tgt] = lchild[li]
-            right_np[tgt] = rchild[li]
-            sdim_np_all[tgt] = sd_np[li]
-            sval_np_all[tgt] = sv_np[li]
-            # next level: keep only members of internal children
+            kids[tgt] = child[:, li].T
+            sdim[tgt] = split_dim.cpu().numpy()[li]
+            sval[tgt] = split_val.cpu().numpy()[li]
+            n_new = int((new_ids >= 0).sum())
+            kids = np.concatenate([kids, np.zeros((n_new, 2), dtype=np.int64)])
+            sdim = np.concatenate([sdim, np.zeros(n_new, dtype=np.int64)])
+            sval = np.concatenate([sval, np.zeros(n_new)])
+            # next level: keep only members of internal children; segment
+            # 2*s + side takes the [2, nseg] arrays interleaved
             seg2 = seg * 2 + side.long()
-            keep_seg = torch.zeros(nseg * 2, dtype=torch.bool, device=device)
-            node_of = torch.full((nseg * 2,), -1, dtype=torch.int64, device=device)
-            kl = torch.as_tensor(child_internal_l, device=device)
-            kr = torch.as_tensor(child_internal_r, device=device)
-            keep_seg[0::2] = kl
-            keep_seg[1::2] = kr
-            node_of[0::2] = torch.as_tensor(new_ids_l, device=device)
-            node_of[1::2] = torch.as_tensor(new_ids_r, device=device)
-            keep = keep_seg[seg2]
+            node_of = torch.as_tensor(new_ids.T.ravel(), device=device)
+            keep = node_of[seg2] >= 0
             perm = perm[keep]
-            seg2 = seg2[keep]
-            uniq, seg = torch.unique(seg2, return_inverse=True)
+            uniq, seg = torch.unique(seg2[keep], return_inverse=True)
             seg_node = node_of[uniq].cpu().numpy()
             nseg = uniq.numel()
-            n = n  # unchanged (total vector count for leaf encoding)
             if nseg == 0:
                 break
             if verbose and level % 8 == 0:
@@ -363,15 +357,13 @@ def build_kdt_tree(vectors, *, ntrees=1, sample_dims=16, seed=2016,
             # a lone point never reaches a split, and a root left at zeros
             # names itself as both children: the search would descend for
             # ever. Leaf 0 on the left, the empty-side leaf on the right.
-            left_np[0] = -1
-            right_np[0] = -(np.int64(n) + 1)
-        nodes = np.zeros((len(left_np), 4), dtype=np.int32)
-        nodes[:, 0] = left_np + np.where(left_np >= 0, base, 0)
-        nodes[:, 1] = right_np + np.where(right_np >= 0, base, 0)
-        nodes[:, 2] = sdim_np_all
-        nodes[:, 3] = sval_np_all.astype(np.float32).view(np.int32)
+            kids[0] = -1, -(np.int64(n) + 1)
+        nodes = np.zeros((len(kids), 4), dtype=np.int32)
+        nodes[:, :2] = kids + np.where(kids >= 0, base, 0)
+        nodes[:, 2] = sdim
+        nodes[:, 3] = sval.astype(np.float32).view(np.int32)
         all_nodes.append(nodes)
-        base += len(left_np)
+        base += len(kids)
     return (np.array(tree_start, dtype=np.int32),
             np.concatenate(all_nodes).astype(np.int32))
 
@@ -381,8 +373,9 @@ def build_kdt_tree(vectors, *, ntrees=1, sample_dims=16, seed=2016,
 # ------------------------------------------------------------------ #
 
 def _tpt_leaves(xf, leaf, gen):
-    """Random-hyperplane tree: returns (perm, [(start, count), ...]) — leaves
-    are contiguous slices of perm."""
+    """Random-hyperplane tree: returns (perm, starts, counts) — leaf i is
+    the slice perm[starts[i] : starts[i] + counts[i]]; built from the
+    segment ids in use, so no leaf is empty."""
     n, d = xf.shape
     perm = torch.arange(n, device=xf.device)
     seg = torch.zeros(n, dtype=torch.int64, device=xf.device)
@@ -390,52 +383,37 @@ def _tpt_leaves(xf, leaf, gen):
     max_size = n
     while max_size > leaf:
         r = torch.randn(d, generator=gen, device=xf.device)
-        proj = xf[perm] @ r
-        o1 = proj.argsort()
-        o2 = seg[o1].argsort(stable=True)
-        order = o1[o2]
+        order = _segmented_order(xf[perm] @ r, seg)
         perm = perm[order]
         seg = seg[order]                      # segments contiguous, proj-sorted
         counts = torch.bincount(seg, minlength=nseg)
-        starts = torch.cumsum(counts, 0) - counts
-        half = counts // 2
-        pos = torch.arange(n, device=xf.device) - starts.repeat_interleave(counts)
-        within_hi = pos >= half.repeat_interleave(counts)
+        within_hi = _pos_in_segment(seg, counts) >= (counts // 2)[seg]
         # only split segments still above the leaf size
-        splitting = (counts > leaf).repeat_interleave(counts)
-        seg = seg * 2 + (within_hi & splitting).long()
+        seg = seg * 2 + (within_hi & (counts > leaf)[seg]).long()
         uniq, seg = torch.unique(seg, return_inverse=True)
         nseg = uniq.numel()
         max_size = int(torch.bincount(seg, minlength=nseg).max().item())
     counts = torch.bincount(seg, minlength=nseg)
-    starts = torch.cumsum(counts, 0) - counts
-    return perm, list(zip(starts.tolist(), counts.tolist()))
+    return perm, _seg_starts(counts), counts
 
 
-def _leaf_knn(xf, perm, bounds, kper, chunk_rows=1_000_000):
+def _leaf_knn(xf, perm, starts, counts, kper, chunk_rows=1_000_000):
     """Exact KNN inside each leaf. Returns (ids int32 [n,kper], dists f32) in
     original vector-id space (L2 on the f32 view; candidate generation only —
     exact metric distances are recomputed by the searcher)."""
     n = xf.shape[0]
     ids = torch.full((n, kper), -1, dtype=torch.int32, device=xf.device)
     dst = torch.full((n, kper), float("inf"), device=xf.device)
-    maxleaf = max(c for _, c in bounds)
-    batch = max(1, chunk_rows // maxleaf)
-    starts_t = torch.tensor([s for s, _ in bounds], device=xf.device)
-    counts_t = torch.tensor([c for _, c in bounds], device=xf.device)
-    for i in range(0, len(bounds), batch):
-        st = starts_t[i:i + batch]
-        ct = counts_t[i:i + batch]
+    m = int(counts.max())
+    for i, j in _chunks(counts.numel(), max(1, chunk_rows // m)):
+        st, ct = starts[i:j], counts[i:j]
         B = st.numel()
-        m = maxleaf
         pos = torch.arange(m, device=xf.device)[None, :].expand(B, m)
         mask = pos < ct[:, None]
         gidx = (st[:, None] + pos).clamp(max=n - 1)
         gather = perm[gidx]                    # [B, m]
         gather = torch.where(mask, gather, torch.zeros_like(gather))
-        pts = xf[gather]                       # [B, m, d]
-        sq = (pts * pts).sum(-1)
-        d2 = sq[:, :, None] + sq[:, None, :] - 2.0 * torch.bmm(pts, pts.transpose(1, 2))
+        d2 = _pairwise_sq_l2(xf[gather])       # [B, m, m]
         d2.diagonal(dim1=1, dim2=2).fill_(float("inf"))
         d2.masked_fill_(~mask[:, None, :], float("inf"))
         k = min(kper, m - 1)
@@ -464,8 +442,7 @@ def _merge_candidates(ids_a, dst_a, ids_b, dst_b, cand, self_ids,
     else:
         out_i = torch.empty((n, cand), dtype=ids_a.dtype, device=ids_a.device)
         out_d = torch.empty((n, cand), dtype=dst_a.dtype, device=dst_a.device)
-    for s in range(0, n, row_chunk):
-        e = min(n, s + row_chunk)
+    for s, e in _chunks(n, row_chunk):
         cid = torch.cat([ids_a[s:e], ids_b[s:e]], dim=1)
         cdd = torch.cat([dst_a[s:e], dst_b[s:e]], dim=1)
         order = cdd.argsort(dim=1, stable=True)
@@ -492,30 +469,120 @@ def _merge_candidates(ids_a, dst_a, ids_b, dst_b, cand, self_ids,
     return out_i, out_d
 
 
+def _bridge_ids(xf, perm, counts):
+    """Highway bridges: the reference's search-based RefineNode pool
+    (CEF=1000, NeighborhoodGraph.h:535) reaches far beyond a point's own
+    cluster, which is what creates the cross-cluster edges the RNG prune
+    then filters. Truncated in-leaf KNN pools cannot (tight clusters
+    become graph islands), so every point gets "bridge" candidates: the
+    medoids of the nearest other TP-tree leaves. They sort to the pool's
+    tail and survive (the pool is widened, not truncated), and the RNG
+    rule decides acceptance exactly as RebuildNeighbors would.
+
+    `perm`, `counts`: one TP-tree partition (_tpt_leaves). Returns int32
+    [n, <= 8], or None when there is no other leaf to bridge to."""
+    n, d = xf.shape
+    device = xf.device
+    L = counts.numel()
+    bknn = min(8, L - 1)
+    if bknn <= 0:
+        return None
+    # an empty leaf would keep the argmin sentinel below and take perm[0]
+    # for its medoid; _tpt_leaves cannot produce one
+    assert int(counts.min()) > 0
+    # Leaf centroids + medoids WITHOUT padded [L, maxleaf, d] tensors
+    # (at 100M/131k leaves those transients alone are ~90 GB and OOM
+    # next to the candidate pools): index_add centroids, then a
+    # packed-key (float-bits<<32 | index) segmented argmin per leaf.
+    leaf_of_perm = torch.repeat_interleave(
+        torch.arange(L, device=device), counts)
+    leaf_of = torch.empty(n, dtype=torch.int64, device=device)
+    leaf_of[perm] = leaf_of_perm
+    centroids = torch.zeros((L, d), device=device)
+    for s, e in _chunks(n, 10_000_000):
+        centroids.index_add_(0, leaf_of_perm[s:e], xf[perm[s:e]])
+    centroids /= counts.float()[:, None]
+    keymin = torch.full((L,), 2 ** 62, dtype=torch.int64, device=device)
+    for s, e in _chunks(n, 10_000_000):
+        lf = leaf_of_perm[s:e]
+        dc = ((xf[perm[s:e]] - centroids[lf]) ** 2).sum(1)
+        # non-negative f32 bit patterns are order-preserving as ints
+        key = (dc.view(torch.int32).to(torch.int64) << 32) | \
+            torch.arange(s, e, device=device)
+        keymin.scatter_reduce_(0, lf, key, reduce="amin")
+    medoid = perm[keymin & 0xffffffff]               # [L]
+    # exponential-rank ladder of nearest leaves: ranks 1,2,4,...: short
+    # bridges link adjacent leaves, long ones cross cluster groups —
+    # scale-independent (at 100M a tight cluster spans many leaves, so
+    # nearest-8 bridges alone stay inside it and islands return).
+    ranks = [1, 2, 4, 8, 16, 32, 64, 128]
+    ranks = [r for r in ranks if r < L][:bknn]
+    kmax = max(ranks) + 1
+    nleaf = torch.empty((L, len(ranks)), dtype=torch.int64, device=device)
+    for s, e in _chunks(L, max(1024, int(2e9 // (L * 4)))):
+        dc = torch.cdist(centroids[s:e], centroids)
+        idxs = dc.topk(kmax + 1, dim=1, largest=False).indices
+        # drop self (rank 0), take the ladder ranks
+        nleaf[s:e] = idxs[:, 1:][:, [r - 1 for r in ranks]]
+    return medoid[nleaf][leaf_of].int()                   # [n, len(ranks)]
+
+
 def _prune_chunk(cand, d):
     """point-chunk size keeping the [B, cand, cand] pairwise tensor ~2GB"""
     return max(4096, int(2e9 // (cand * cand * 4 + cand * d * 8)))
 
 
+def _rng_prune(xf, cid, cdd, degree, rng_factor, fill_pruned=False):
+    """RNG prune candidate lists (ascending by dist), any number of rows:
+    this is the one place that sizes the [B, C, C] pairwise tensor. Rows
+    are pruned independently, so the sub-chunking never shows in the result.
+
+    fill_pruned: after the RNG rule fills what it can, pad remaining degree
+    slots with the nearest REJECTED candidates (build-quality knob for
+    billion-scale pools, cf. HNSW keepPrunedConnections; the reference's
+    RebuildNeighbors pads -1 — its CEF=1000 pools rarely leave slots empty,
+    shallow pools at 100M+ do)."""
+    out = torch.full((cid.shape[0], degree), -1, dtype=torch.int32,
+                     device=cid.device)
+    C = cid.shape[1]
+    for s, e in _chunks(cid.shape[0], _prune_chunk(C, xf.shape[1])):
+        ci, cd = cid[s:e], cdd[s:e]
+        P = _pairwise_sq_l2(xf[ci.clamp(min=0).long()])
+        valid = torch.isfinite(cd)
+        acc = torch.zeros_like(valid)
+        count = torch.zeros(e - s, dtype=torch.int32, device=cid.device)
+        for j in range(C):
+            viol = (rng_factor * P[:, :, j] < cd[:, j:j + 1]) & acc
+            good = valid[:, j] & ~viol.any(1) & (count < degree)
+            acc[:, j] = good
+            count += good.int()
+        if fill_pruned:
+            # fill leftover slots with the nearest valid rejected candidates
+            free = (degree - count).clamp(min=0)
+            rej = valid & ~acc
+            rej_rank = torch.cumsum(rej.int(), dim=1)
+            acc = acc | (rej & (rej_rank <= free[:, None]))
+        pos = (torch.cumsum(acc.int(), dim=1) - 1).clamp(min=0)
+        rows = torch.nonzero(acc, as_tuple=True)
+        out[s:e][rows[0], pos[rows]] = ci[rows]
+    return out
+
+
 def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
                     rng_factor=1.0, seed=2016, device=None, point_chunk=None,
                     verbose=False):
-    """Returns graph int32 [n, degree] (RNG-pruned, ascending, -1 padded)."""
-    device = device or _dev()
-    n = vectors.shape[0]
-    xf = torch.as_tensor(vectors, device=device)
-    if xf.dtype != torch.float32:
-        xf = xf.float()
-    gen = torch.Generator(device=device)
-    gen.manual_seed(seed + 77)
+    """Returns (graph, cand_ids, cand_dst), tensors on the device: graph
+    int32 [n, degree] (RNG-pruned, ascending, -1 padded) and the [n, cand]
+    candidate pools it was pruned from, which the refine steps grow."""
+    device, xf, gen = _prologue(vectors, device, seed + 77)
+    n = xf.shape[0]
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
 
     kper = min(max(33, cand // max(ntrees, 1)), 64)
     ids = dst = None
-    last_partition = None
     for t in range(ntrees):
-        perm, bounds = _tpt_leaves(xf, tpt_leaf, gen)
-        tids, tdst = _leaf_knn(xf, perm, bounds, kper)
+        perm, starts, counts = _tpt_leaves(xf, tpt_leaf, gen)
+        tids, tdst = _leaf_knn(xf, perm, starts, counts, kper)
         if ids is None:
             ids, dst = _merge_candidates(tids, tdst, tids[:, :0], tdst[:, :0],
                                          cand, self_ids)
@@ -523,72 +590,16 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
             ids, dst = _merge_candidates(ids, dst, tids, tdst, cand, self_ids,
                                          out=(ids, dst))
         del tids, tdst
-        last_partition = (perm, bounds)
         if verbose:
-            print(f"  tpt tree {t + 1}/{ntrees} merged ({len(bounds)} leaves)")
+            print(f"  tpt tree {t + 1}/{ntrees} merged ({counts.numel()} leaves)")
 
-    # Highway bridges: the reference's search-based RefineNode pool
-    # (CEF=1000, NeighborhoodGraph.h:535) reaches far beyond a point's own
-    # cluster, which is what creates the cross-cluster edges the RNG prune
-    # then filters. Truncated in-leaf KNN pools cannot (tight clusters
-    # become graph islands), so append per-point "bridge" candidates: the
-    # medoids of the nearest other TP-tree leaves. They sort to the pool's
-    # tail and survive (the pool is widened, not truncated), and the RNG
-    # rule decides acceptance exactly as RebuildNeighbors would.
-    perm, bounds = last_partition
-    L = len(bounds)
-    bknn = min(8, L - 1)
-    bridge_ids = None
-    if bknn > 0:
-        # Leaf centroids + medoids WITHOUT padded [L, maxleaf, d] tensors
-        # (at 100M/131k leaves those transients alone are ~90 GB and OOM
-        # next to the candidate pools): index_add centroids, then a
-        # packed-key (float-bits<<32 | index) segmented argmin per leaf.
-        d = xf.shape[1]
-        counts_t = torch.tensor([c for _, c in bounds], device=device)
-        leaf_of_perm = torch.repeat_interleave(
-            torch.arange(L, device=device), counts_t)
-        leaf_of = torch.empty(n, dtype=torch.int64, device=device)
-        leaf_of[perm] = leaf_of_perm
-        centroids = torch.zeros((L, d), device=device)
-        pc = 10_000_000
-        for s0 in range(0, n, pc):
-            e0 = min(n, s0 + pc)
-            centroids.index_add_(0, leaf_of_perm[s0:e0], xf[perm[s0:e0]])
-        centroids /= counts_t.float().clamp(min=1)[:, None]
-        keymin = torch.full((L,), 2 ** 62, dtype=torch.int64, device=device)
-        for s0 in range(0, n, pc):
-            e0 = min(n, s0 + pc)
-            lf = leaf_of_perm[s0:e0]
-            dc = ((xf[perm[s0:e0]] - centroids[lf]) ** 2).sum(1)
-            # non-negative f32 bit patterns are order-preserving as ints
-            key = (dc.view(torch.int32).to(torch.int64) << 32) | \
-                torch.arange(s0, e0, device=device)
-            keymin.scatter_reduce_(0, lf, key, reduce="amin")
-        medoid = perm[keymin & 0xffffffff]               # [L]
-        # exponential-rank ladder of nearest leaves: ranks 1,2,4,...: short
-        # bridges link adjacent leaves, long ones cross cluster groups —
-        # scale-independent (at 100M a tight cluster spans many leaves, so
-        # nearest-8 bridges alone stay inside it and islands return).
-        ranks = [1, 2, 4, 8, 16, 32, 64, 128]
-        ranks = [r for r in ranks if r < L][:bknn]
-        kmax = max(ranks) + 1
-        nleaf = torch.empty((L, len(ranks)), dtype=torch.int64, device=device)
-        lchunk = max(1024, int(2e9 // (L * 4)))
-        for s0 in range(0, L, lchunk):
-            e0 = min(L, s0 + lchunk)
-            dc = torch.cdist(centroids[s0:e0], centroids)
-            idxs = dc.topk(kmax + 1, dim=1, largest=False).indices
-            # drop self (rank 0), take the ladder ranks
-            nleaf[s0:e0] = idxs[:, 1:][:, [r - 1 for r in ranks]]
-        bridge_ids = medoid[nleaf][leaf_of].int()             # [n, len(ranks)]
-        del leaf_of_perm, keymin, centroids
-
+    bridge_ids = _bridge_ids(xf, perm, counts)     # over the last partition
     if point_chunk is None:
-        point_chunk = _prune_chunk(cand, xf.shape[1])
+        # the width _rng_prune will see, so that it never splits a chunk
+        wide = cand + (0 if bridge_ids is None else bridge_ids.shape[1])
+        point_chunk = _prune_chunk(wide, xf.shape[1])
     graph = torch.full((n, degree), -1, dtype=torch.int32, device=device)
-    for s in range(0, n, point_chunk):
-        e = min(n, s + point_chunk)
+    for s, e in _chunks(n, point_chunk):
         cid, cdd = ids[s:e], dst[s:e]
         if bridge_ids is not None:
             bi = bridge_ids[s:e]
@@ -597,56 +608,10 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
             cid, cdd = _merge_candidates(cid, cdd, bi, bd,
                                          cid.shape[1] + bi.shape[1],
                                          self_ids[s:e])
-        graph[s:e] = _rng_prune(xf, cid, cdd, degree, rng_factor, device)
+        graph[s:e] = _rng_prune(xf, cid, cdd, degree, rng_factor)
         if verbose and (s // point_chunk) % 20 == 0:
             print(f"  rng prune {e}/{n}")
     return graph, ids, dst
-
-
-def _rng_prune(xf, cid, cdd, degree, rng_factor, device, fill_pruned=False):
-    """RNG prune one chunk of candidate lists (ascending by dist).
-
-    fill_pruned: after the RNG rule fills what it can, pad remaining degree
-    slots with the nearest REJECTED candidates (build-quality knob for
-    billion-scale pools, cf. HNSW keepPrunedConnections; the reference's
-    RebuildNeighbors pads -1 — its CEF=1000 pools rarely leave slots empty,
-    shallow pools at 100M+ do)."""
-    C = cid.shape[1]
-    cvec = xf[cid.clamp(min=0).long()]
-    csq = (cvec * cvec).sum(-1)
-    P = csq[:, :, None] + csq[:, None, :] - 2.0 * torch.bmm(cvec, cvec.transpose(1, 2))
-    valid = torch.isfinite(cdd)
-    acc = torch.zeros_like(valid)
-    count = torch.zeros(cid.shape[0], dtype=torch.int32, device=device)
-    for j in range(C):
-        viol = (rng_factor * P[:, :, j] < cdd[:, j:j + 1]) & acc
-        good = valid[:, j] & ~viol.any(1) & (count < degree)
-        acc[:, j] = good
-        count += good.int()
-    if fill_pruned:
-        # fill leftover slots with the nearest valid rejected candidates
-        free = (degree - count).clamp(min=0)
-        rej = valid & ~acc
-        rej_rank = torch.cumsum(rej.int(), dim=1)
-        acc = acc | (rej & (rej_rank <= free[:, None]))
-    out = torch.full((cid.shape[0], degree), -1, dtype=torch.int32, device=device)
-    pos = (torch.cumsum(acc.int(), dim=1) - 1).clamp(min=0)
-    rows = torch.nonzero(acc, as_tuple=True)
-    out[rows[0], pos[rows]] = cid[rows]
-    return out
-
-
-def _rng_prune_rows(xf, cid, cdd, degree, rng_factor, device,
-                    fill_pruned=False):
-    """_rng_prune over row sub-chunks (the [B, C, C] pairwise tensor is the
-    memory driver; C can be wider than the stored pool here)."""
-    pc = _prune_chunk(cid.shape[1], xf.shape[1])
-    out = torch.empty((cid.shape[0], degree), dtype=torch.int32, device=device)
-    for s in range(0, cid.shape[0], pc):
-        e = min(cid.shape[0], s + pc)
-        out[s:e] = _rng_prune(xf, cid[s:e], cdd[s:e], degree, rng_factor,
-                              device, fill_pruned=fill_pruned)
-    return out
 
 
 def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
@@ -657,16 +622,13 @@ def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
     (NeighborhoodGraph.h:460-560 RefineGraph/RefineNode). Here the pool is
     grown NN-descent style — current candidates + two-hop neighbors +
     reverse edges — then RNG-pruned with the same RebuildNeighbors rule.
-    Returns (graph int32 [n, degree], cand_ids, cand_dst)."""
-    device = device or _dev()
-    n = vectors.shape[0]
-    xf = torch.as_tensor(vectors, device=device)
-    if xf.dtype != torch.float32:
-        xf = xf.float()
+    Returns (graph int32 [n, degree], cand_ids, cand_dst), all tensors on
+    the device (the graph used to come back as a numpy array); a graph
+    tensor already on the device, and the pools, are updated in place."""
+    device, xf, _ = _prologue(vectors, device, seed + 123)
+    n = xf.shape[0]
     g = torch.as_tensor(graph, device=device)
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
-    gen = torch.Generator(device=device)
-    gen.manual_seed(seed + 123)
     if point_chunk is None:
         point_chunk = _prune_chunk(cand, xf.shape[1])
 
@@ -678,21 +640,19 @@ def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
         # transients. NN-descent only needs a reverse SAMPLE per node.
         rcap = 16
         rev = torch.full((n, rcap), -1, dtype=torch.int32, device=device)
-        edge_chunk = 64_000_000
         deg = g.shape[1]
-        for es in range(0, n, max(1, edge_chunk // deg)):
-            ee = min(n, es + max(1, edge_chunk // deg))
+        for es, ee in _chunks(n, max(1, 64_000_000 // deg)):
             srcc = self_ids[es:ee].repeat_interleave(deg)
             dstc = g[es:ee].reshape(-1).long()
             keep = dstc >= 0
             srcc, dstc = srcc[keep], dstc[keep]
             slot = ((srcc.long() * 2654435761) + r * 97) % rcap
             rev[dstc, slot] = srcc
-        for s in range(0, n, point_chunk):
-            e = min(n, s + point_chunk)
-            B = e - s
+        # g is read (hop-2) while it is rewritten chunk by chunk: the chunk
+        # boundaries are part of the result
+        for s, e in _chunks(n, point_chunk):
             nbr = g[s:e]                                   # [B, deg]
-            hop2 = g[nbr[:, :hop_sample].clamp(min=0).long()].reshape(B, -1)
+            hop2 = g[nbr[:, :hop_sample].clamp(min=0).long()].reshape(e - s, -1)
             hop2 = torch.where((nbr[:, :hop_sample] < 0).repeat_interleave(
                 g.shape[1], dim=1), torch.full_like(hop2, -1), hop2)
             newc = torch.cat([hop2, rev[s:e]], dim=1)
@@ -700,10 +660,10 @@ def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
             cand_ids[s:e], cand_dst[s:e] = _merge_candidates(
                 cand_ids[s:e], cand_dst[s:e], newc, newd, cand, self_ids[s:e])
             g[s:e] = _rng_prune(xf, cand_ids[s:e], cand_dst[s:e], degree,
-                                rng_factor, device)
+                                rng_factor)
         if verbose:
             print(f"  refine round {r + 1}/{rounds} done")
-    return g.cpu().numpy(), cand_ids, cand_dst
+    return g, cand_ids, cand_dst
 
 
 def _exact_l2(xf, q_rows, c_ids):
@@ -730,7 +690,9 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
     uses CEF=1000; k=64 measured ineffective at 30M — 0.664 vs 0.649
     baseline), hence k=512 / max_check=8192 defaults. GPU-only (the
     searcher has no CPU path); vectors_t is the normalized torch tensor on
-    the device; cand lists are the builder's pools (merged in)."""
+    the device; graph is a tensor on that device; cand lists are the
+    builder's pools (merged in). All three are updated in place and
+    returned."""
     import sptag_amd
     device = vectors_t.device
     n = vectors_t.shape[0]
@@ -749,7 +711,8 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
                     int(12e9 // (max_check * 40 * 8)))
         chunk = max(16_384, chunk)
     x_np = vectors_t.cpu().numpy()
-    graph_t = torch.as_tensor(graph, device=device)         if not torch.is_tensor(graph) else graph
+    create = (sptag_amd.AnnIndex.FromArraysKDT if algo == "KDT"
+              else sptag_amd.AnnIndex.FromArrays)
     # Search distances arrive in the index metric; the builder's pools are
     # L2 on the (normalized) float view. For cosine the EXACT conversion is
     # L2(q,v) = |q|^2 + |v|^2 - 2*dot with dot = base^2 - d_search.
@@ -759,16 +722,11 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
     nsq = (xf * xf).sum(1) if distmethod == "Cosine" else None
     base2 = (127.0 * 127.0) if vectors_t.dtype == torch.int8 else 1.0
     for r in range(rounds):
-        if algo == "KDT":
-            ix = sptag_amd.AnnIndex.FromArraysKDT(
-                x_np, tree_start, tree_nodes, graph_t.cpu().numpy(), distmethod)
-        else:
-            ix = sptag_amd.AnnIndex.FromArrays(
-                x_np, tree_start, tree_nodes, graph_t.cpu().numpy(), distmethod)
+        ix = create(x_np, tree_start, tree_nodes, graph.cpu().numpy(),
+                    distmethod)
         d_vids = torch.empty((chunk, k), dtype=torch.int32, device=device)
         d_dists = torch.empty((chunk, k), dtype=torch.float32, device=device)
-        for s0 in range(0, n, chunk):
-            e0 = min(n, s0 + chunk)
+        for s0, e0 in _chunks(n, chunk):
             B = e0 - s0
             q = vectors_t[s0:e0].contiguous()
             ix.BatchSearchDevice(q.data_ptr(), B, k, d_vids.data_ptr(),
@@ -795,8 +753,8 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
             wide = cand + sv_s.shape[1]
             wi, wd = _merge_candidates(cand_ids[s0:e0], cand_dst[s0:e0],
                                        sv_s, sd_s, wide, self_ids[s0:e0])
-            graph_t[s0:e0] = _rng_prune_rows(xf, wi, wd, degree, rng_factor,
-                                             device, fill_pruned=fill_pruned)
+            graph[s0:e0] = _rng_prune(xf, wi, wd, degree, rng_factor,
+                                      fill_pruned=fill_pruned)
             cand_ids[s0:e0] = wi[:, :cand]
             cand_dst[s0:e0] = wd[:, :cand]
             del wi, wd
@@ -806,7 +764,7 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
         torch.cuda.empty_cache()
         if verbose:
             print(f"  search-refine round {r + 1}/{rounds} done")
-    return graph_t, cand_ids, cand_dst
+    return graph, cand_ids, cand_dst
 
 
 def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
@@ -836,7 +794,6 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
         graph, cids, cdst = refine_graph(
             vectors, graph, cids, cdst, degree=degree, cand=cand,
             rounds=refine_rounds, device=device, seed=seed, verbose=verbose)
-        graph = torch.as_tensor(graph, device=device or _dev())
     if search_refine_rounds > 0 and torch.cuda.is_available():
         xt = torch.as_tensor(vectors, device=device or _dev())
         graph, cids, cdst = refine_via_search(
@@ -845,7 +802,6 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
             max_check=srefine_mc, fill_pruned=fill_pruned,
             rounds=search_refine_rounds, verbose=verbose)
         del xt
-    graph = graph.cpu().numpy() if torch.is_tensor(graph) else graph
     return {"vectors": vectors, "tree_start": tree_start,
-            "tree_nodes": tree_nodes, "graph": graph,
+            "tree_nodes": tree_nodes, "graph": graph.cpu().numpy(),
             "distmethod": distmethod, "algo": algo}
