@@ -38,6 +38,9 @@ struct SearchCfg {
     int32_t search_dup;          /* searchDuplicated (BKT dispatch bit 1) */
     int32_t search_deleted;      /* searchDeleted (dispatch bit 2) */
     int32_t ng_cap, spt_cap, dpq_cap;  /* heap capacities (entries) */
+    int32_t ng_lsplit;   /* LDS pass: NG heap entries [0..ng_lsplit] live in
+                            LDS, the rest in the query's gheap_ng slab;
+                            == ng_cap keeps the whole heap in LDS */
     int32_t vcap;                      /* visited table slots (pow2) */
     int32_t spec_flags;  /* perf-only speculation (identical results):
                             bit0 = warm neighbor vector lines during the
@@ -63,12 +66,17 @@ struct SearchBufs {
     int32_t* visited;      /* nq*vcap, zeroed before launch */
     int32_t* oflow;        /* nq flags: nonzero => rerun with bigger caps */
     int32_t* stats;        /* nq*2: {checked, popped} per query (may be null) */
-    /* only used by the global-heap variant: per-query strided scratch */
+    /* per-query strided scratch: the whole heap in the global-heap variant,
+     * the tail below the LDS tier in the LDS pass (gheap_ng may be null
+     * there when ng_lsplit == ng_cap) */
     void* gheap_ng;        /* nq * (ng_cap+1) * 8B */
     void* gheap_spt;       /* nq * (spt_cap+1) * 8B */
 };
 
 enum { SPT_LDS_TIER_H = 255 };  /* SPT heap LDS tier entries (see kernels) */
+enum { NG_GLEVELS = 3 };  /* NG heap: deepest levels kept in global memory in
+                             the LDS pass (see ng_lds_split); chosen by
+                             measurement, profiles/occupancy_ng_tier.txt */
 enum { SERIAL_STATE_BYTES = 64 };  /* LDS slot of the kernels' SerialState */
 
 #ifdef __HIPCC__
@@ -85,9 +93,9 @@ struct LdsLayout {
 };
 
 /* nstage: staged candidates (dstage + istage entries each); dpq_cap < 0: no
- * results queue in LDS; ng_cap == 0: no NG heap in LDS. */
+ * results queue in LDS; ng_lds: NG heap entries [0..ng_lds] in LDS, 0: none. */
 SPTAG_HD inline LdsLayout lds_layout(int dim, size_t esz, int k, int nstage,
-                                     int dpq_cap, bool spt_tier, int ng_cap)
+                                     int dpq_cap, bool spt_tier, int ng_lds)
 {
     LdsLayout l;
     uint32_t b = 0;
@@ -98,7 +106,7 @@ SPTAG_HD inline LdsLayout lds_layout(int dim, size_t esz, int k, int nstage,
     l.dpq = b;      if (dpq_cap >= 0) b += ((uint32_t)dpq_cap + 1) * 4;  /* DistPriorityQueue */
     l.ss = b;       b += SERIAL_STATE_BYTES;               /* scalar slots, padding */
     l.spt_tier = b; if (spt_tier) b += ((uint32_t)SPT_LDS_TIER_H + 1) * 8;
-    l.ng = b;       if (ng_cap > 0) b += ((uint32_t)ng_cap + 1) * 8;  /* SPT heap tail is global */
+    l.ng = b;       if (ng_lds > 0) b += ((uint32_t)ng_lds + 1) * 8;  /* heap tails are global */
     l.total = b;
     return l;
 }
@@ -107,7 +115,19 @@ SPTAG_HD inline LdsLayout lds_layout(int dim, size_t esz, int k, int nstage,
 inline size_t lds_bytes(int dim, size_t esz, const SearchCfg& c, bool heaps_in_lds)
 {
     return lds_layout(dim, esz, c.k, MAX_DEG, c.dpq_cap, true,
-                      heaps_in_lds ? c.ng_cap : 0).total;
+                      heaps_in_lds ? c.ng_lsplit : 0).total;
+}
+
+/* NG heap entries kept in LDS when the deepest `glevels` levels of a heap
+ * filled to `ng_cap` go to global memory: every shallower level stays, so
+ * the split is the last index of a level. glevels 0 keeps the whole heap. */
+inline int32_t ng_lds_split(int32_t ng_cap, int glevels)
+{
+    if (glevels <= 0 || ng_cap <= 0) return ng_cap;
+    int32_t lastlevel = 1;             /* first index of the deepest level */
+    while (lastlevel * 2 <= ng_cap) lastlevel *= 2;
+    int32_t first_global = lastlevel >> (glevels - 1);
+    return first_global > 1 ? first_global - 1 : 1;   /* the root stays in LDS */
 }
 
 /* iterative search: results queue and both heaps persist in global memory */

@@ -116,7 +116,7 @@ struct HostIndex {
     int64_t deleted_count = 0;
     std::mutex lock;
     /* cached per-handle search scratch (grow-only) */
-    DevBuf d_visited, d_oflow, d_stats, d_gng, d_gspt, d_redo, d_gspt0;
+    DevBuf d_visited, d_oflow, d_stats, d_gng, d_gspt, d_redo, d_gspt0, d_gng0;
     DevEvents ev;
     double last_kernel_ms = 0;
     long long last_checked = 0, last_popped = 0;
@@ -482,7 +482,7 @@ static SearchCfg base_cfg(const SptagAmdIndex* ix, int32_t nq, int32_t k,
     cfg.search_dup = refine ? 0 : 1;
     cfg.search_deleted = refine ? 1 : 0;
     cfg.dpq_cap = std::max(max_check / 16, k);   /* WorkSpace.h:268 */
-    cfg.vcap = cfg.ng_cap = cfg.spt_cap = 0;
+    cfg.vcap = cfg.ng_cap = cfg.spt_cap = cfg.ng_lsplit = 0;
     /* measured on MI355X (profiles/round2_experiments/ab_v5.txt): both
      * speculation forms LOSE throughput at 10M/mc2048 (745k QPS off vs 622k
      * on) — the extra touch loads consume request bandwidth the resident
@@ -600,15 +600,31 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
      * so they are cut to the reference's. */
     cfg.ng_cap = std::min(cfg.ng_cap, max_check * 30);
     cfg.spt_cap = std::min(cfg.spt_cap, max_check * 10);
+    /* Only the top levels of the frontier heap stay in LDS; the deepest
+     * NG_GLEVELS levels of a heap filled to ng_cap live in a per-query
+     * global slab. The headroom above the typical occupancy (~0.25 x
+     * MaxCheck) is what keeps the rerun rare, and it is mostly empty: in
+     * LDS it bought nothing but a lower count of resident queries per CU.
+     * Storage placement only — capacity and overflow are unchanged. */
+    int glevels = NG_GLEVELS;
+    if (const char* e = getenv("SPTAG_AMD_NG_GLEVELS"))   /* perf experiments */
+        glevels = std::min(3, std::max(0, atoi(e)));
+    cfg.ng_lsplit = ng_lds_split(cfg.ng_cap, glevels);
     /* phase-cycle diagnostic (BKT kernels only — the KDT kernel writes
      * plain stride-2 stats) */
     cfg.prof = (getenv("SPTAG_AMD_PROF") && ix->algo == ALGO_BKT) ? 1 : 0;
     const int sstride = cfg.prof ? PROF_STATS : 2;
 
+    /* The LDS pass runs only while its footprint stays within 64 KiB (and
+     * the device's own per-block limit): beyond that too few queries are
+     * resident per CU for it to pay, and the bound does not depend on what
+     * the device reports. */
     int lds_limit = 64 * 1024;
     (void)hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock,
                                 ix->device);
+    lds_limit = std::min(lds_limit, 64 * 1024);
     bool lds_ok = lds_bytes(ix->dim, ix->esz(), cfg, true) <= (size_t)lds_limit;
+    const bool ng_tail = lds_ok && cfg.ng_lsplit < cfg.ng_cap;
 
     HIP_OR_FAIL(ix->d_visited.ensure((size_t)nq * cfg.vcap * 4), SPTAG_AMD_ERR_OOM);
     HIP_OR_FAIL(ix->d_oflow.ensure((size_t)nq * 4), SPTAG_AMD_ERR_OOM);
@@ -616,6 +632,9 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
     ix->ev.ensure();
     HIP_OR_FAIL(ix->d_gspt0.ensure((size_t)nq * ((size_t)cfg.spt_cap + 1) * 8),
                 SPTAG_AMD_ERR_OOM);
+    if (ng_tail)
+        HIP_OR_FAIL(ix->d_gng0.ensure((size_t)nq * ((size_t)cfg.ng_cap + 1) * 8),
+                    SPTAG_AMD_ERR_OOM);
 
     SearchBufs bufs;
     bufs.queries = d_q;
@@ -624,7 +643,7 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
     bufs.visited = ix->d_visited.as<int32_t>();
     bufs.oflow = ix->d_oflow.as<int32_t>();
     bufs.stats = ix->d_stats.as<int32_t>();
-    bufs.gheap_ng = nullptr;
+    bufs.gheap_ng = ng_tail ? ix->d_gng0.as() : nullptr;
     bufs.gheap_spt = ix->d_gspt0.as();
 
     ix->last_kernel_ms = 0;

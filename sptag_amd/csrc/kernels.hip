@@ -22,7 +22,8 @@
  *     probed in parallel with atomicCAS (set semantics only, order-free);
  *   - distances: 16-lane groups, 4 candidates in flight per wave.
  *
- * HEAPS_IN_LDS=true keeps the NG/SPT frontier heaps in LDS with reduced
+ * HEAPS_IN_LDS=true keeps the top levels of the NG/SPT frontier heaps in LDS
+ * (tails in per-query global slabs) with reduced
  * capacities; if a heap would exceed its reduced capacity while the
  * reference's (30*maxCheck / 10*maxCheck, WorkSpace.h:265) would not, the
  * query sets an overflow flag and the host reruns it with the global-memory
@@ -309,20 +310,37 @@ DEV float dist_f32_fix(const float* __restrict__ q, const float* __restrict__ v)
     return y.reduce_with([&](int c) { return x.y[c]; });
 }
 
-template <int DM>
+/* Dimension class of a float kernel instantiation. A kernel's register
+ * allocation is the maximum over all its code paths, and the fully unrolled
+ * 768-wide form holds 2 x 48 floats live: compiled into the same kernel it
+ * costs a d=128 launch 77 VGPRs (146 against 69) for a form that launch
+ * never runs. So each float kernel exists once per class, holding only that
+ * class's fixed forms plus the generic rolled one, and the launchers pick
+ * the class from the index's dim. The int8 kernels have no fixed forms and
+ * exist once, as DC_SMALL. */
+enum { DC_SMALL = 0, DC_LARGE = 1 };
+enum { DC_SMALL_MAX_DIM = 128 };   /* float dims above this launch DC_LARGE */
+
+template <int DM, int DC>
 DEV float ref_dist_grp_f32(const float* __restrict__ q,
                            const float* __restrict__ v, int d)
 {
-    switch (d) {
-    case 32:  return dist_f32_fix<DM, 32>(q, v);
-    case 48:  return dist_f32_fix<DM, 48>(q, v);
-    case 64:  return dist_f32_fix<DM, 64>(q, v);
-    case 96:  return dist_f32_fix<DM, 96>(q, v);
-    case 128: return dist_f32_fix<DM, 128>(q, v);
-    case 256: return dist_f32_fix<DM, 256>(q, v);
-    case 512: return dist_f32_fix<DM, 512>(q, v);
-    case 768: return dist_f32_fix<DM, 768>(q, v);
-    default: break;
+    if constexpr (DC == DC_SMALL) {
+        switch (d) {
+        case 32:  return dist_f32_fix<DM, 32>(q, v);
+        case 48:  return dist_f32_fix<DM, 48>(q, v);
+        case 64:  return dist_f32_fix<DM, 64>(q, v);
+        case 96:  return dist_f32_fix<DM, 96>(q, v);
+        case 128: return dist_f32_fix<DM, 128>(q, v);
+        default: break;
+        }
+    } else {
+        switch (d) {
+        case 256: return dist_f32_fix<DM, 256>(q, v);
+        case 512: return dist_f32_fix<DM, 512>(q, v);
+        case 768: return dist_f32_fix<DM, 768>(q, v);
+        default: break;
+        }
     }
     const int g = threadIdx.x & 15;
     float a = 0.0f;
@@ -392,11 +410,11 @@ DEV float ref_dist_grp_i8(const int8_t* __restrict__ q,
     return (DM == DM_L2) ? (float)s : (float)(16129 - s);
 }
 
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 DEV float ref_dist_grp(const T* q, const T* v, int d)
 {
     if constexpr (sizeof(T) == 4)
-        return ref_dist_grp_f32<DM>((const float*)q, (const float*)v, d);
+        return ref_dist_grp_f32<DM, DC>((const float*)q, (const float*)v, d);
     else
         return ref_dist_grp_i8<DM>((const int8_t*)q, (const int8_t*)v, d);
 }
@@ -480,8 +498,12 @@ DEV void write_topk(QRes* qrs, int k, int q, int32_t* out_vids, float* out_dists
     }
 }
 
-/* Frontier heaps of the batched search kernels. NG: in LDS at its reduced
- * capacity (LDSHEAP) or in global scratch. SPT (tree) heap: hot top levels
+/* Frontier heaps of the batched search kernels. NG: at its reduced capacity
+ * (LDSHEAP) entries [0..ng_lsplit] sit in LDS and the tail, if the host
+ * chose a split below the capacity, in this query's global slab; the
+ * global-heap variant keeps the whole heap in the slab. The capacity is the
+ * total either way, so overflow means what it meant with the heap all in
+ * LDS. SPT (tree) heap: hot top levels
  * in an LDS tier, tail in global scratch — full reference capacity without
  * the LDS cost of the whole heap (its all-global round-1 form made the seed
  * phase 41.5% of kernel cycles). */
@@ -491,9 +513,11 @@ DEV void search_heaps(const SearchCfg& cfg, const SearchBufs& bufs, const LdsLay
 {
     extern __shared__ char smem[];
     ng.cap = cfg.ng_cap;  ng.ref_cap = cfg.max_check * 30;   /* WorkSpace.h:265 */
-    ng.lds = nullptr; ng.lsplit = 0;
-    ng.a = LDSHEAP ? (NodeDist*)(smem + L.ng)
-                   : (NodeDist*)bufs.gheap_ng + (size_t)q * (cfg.ng_cap + 1);
+    ng.lds = LDSHEAP ? (NodeDist*)(smem + L.ng) : nullptr;
+    ng.lsplit = LDSHEAP ? cfg.ng_lsplit : 0;
+    /* with ng_lsplit == ng_cap no index reaches `a` and the host passes no slab */
+    ng.a = bufs.gheap_ng ? (NodeDist*)bufs.gheap_ng + (size_t)q * (cfg.ng_cap + 1)
+                         : nullptr;
     spt.cap = cfg.spt_cap; spt.ref_cap = cfg.max_check * 10;
     spt.a = (NodeDist*)bufs.gheap_spt + (size_t)q * (cfg.spt_cap + 1);
     spt.lds = (NodeDist*)(smem + L.spt_tier);
@@ -551,10 +575,10 @@ DEV void stage_dists_pipe_f32(QCtx<float>& c, int cnt)
 
 /* stage distances of `cnt` (<=64) data vectors whose ids are in istage[0..cnt)
  * into dstage[0..cnt); whole-wave cooperative, 4 candidates in flight. */
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 DEV void stage_dists(QCtx<T>& c, int cnt)
 {
-    if constexpr (sizeof(T) == 4) {
+    if constexpr (sizeof(T) == 4 && DC == DC_SMALL) {
         QCtx<float>& cf = reinterpret_cast<QCtx<float>&>(c);
         switch (c.di->dim) {
         /* pipelining holds 2 fragments (2*C VGPRs) live; C <= 8 only */
@@ -569,7 +593,7 @@ DEV void stage_dists(QCtx<T>& c, int cnt)
     for (int r = 0; r < cnt; r += 4) {
         int j = r + (c.lane >> 4);
         if (j < cnt) {
-            float dv = ref_dist_grp<T, DM>(c.qlds, vec_at<T>(*c.di, c.istage[j]), c.di->dim);
+            float dv = ref_dist_grp<T, DM, DC>(c.qlds, vec_at<T>(*c.di, c.istage[j]), c.di->dim);
             if ((c.lane & 15) == 0) c.dstage[j] = dv;
         }
     }
@@ -604,23 +628,23 @@ DEV void spt_warm_parents(QCtx<T>& c, int cnt)
  * one of them is needed (no speculation waste), so the 16 round-pipeline
  * latencies collapse into one. Seed-phase tree-center gathers were 31% of
  * kernel cycles. */
-template <typename T, int DM, bool TOUCH>
+template <typename T, int DM, int DC, bool TOUCH>
 DEV void stage_child_dists(QCtx<T>& c, int base, int cnt)
 {
     if (c.lane < cnt) c.istage[c.lane] = c.di->tree_nodes[(size_t)(base + c.lane) * 3];
     __syncthreads();
     uint32_t ts = 0;
     if (TOUCH && c.lane < cnt) ts = touch_lines<T>(*c.di, c.istage[c.lane]);
-    stage_dists<T, DM>(c, cnt);
+    stage_dists<T, DM, DC>(c, cnt);
     /* sink after the staging so the touches and the first rounds overlap */
     if constexpr (TOUCH) asm volatile("" :: "v"(ts));
 }
 
 /* One chunk of a BKT node's children into the SPT heap (lane 0 inserts). */
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 DEV void stage_children(QCtx<T>& c, int base, int cnt)
 {
-    stage_child_dists<T, DM, true>(c, base, cnt);
+    stage_child_dists<T, DM, DC, true>(c, base, cnt);
     spt_warm_parents(c, cnt);
     if (c.lane == 0)
         for (int i = 0; i < cnt; i++)
@@ -630,7 +654,7 @@ DEV void stage_children(QCtx<T>& c, int base, int cnt)
 }
 
 /* BKTree.h:772 SearchTrees — wave-cooperative, serial decisions on lane 0. */
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 DEV void search_trees_dev(QCtx<T>& c, int limit)
 {
     const DevIndex& di = *c.di;
@@ -660,14 +684,14 @@ DEV void search_trees_dev(QCtx<T>& c, int limit)
                 }
             }
             for (int base = cs; base < ce; base += 64)
-                stage_children<T, DM>(c, base, min(64, ce - base));
+                stage_children<T, DM, DC>(c, base, min(64, ce - base));
         }
     }
     __syncthreads();
 }
 
 /* BKTree.h:697 InitSearchTrees (m_bfs = 0). */
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 DEV void init_search_trees_dev(QCtx<T>& c)
 {
     const DevIndex& di = *c.di;
@@ -678,14 +702,14 @@ DEV void init_search_trees_dev(QCtx<T>& c)
         int32_t ce = di.tree_nodes[(size_t)root * 3 + 2];
         if (cs < 0) {
             if (c.lane < 16) {
-                float dv = ref_dist_grp<T, DM>(c.qlds, vec_at<T>(di, center), di.dim);
+                float dv = ref_dist_grp<T, DM, DC>(c.qlds, vec_at<T>(di, center), di.dim);
                 if (c.lane == 0)
                     ndheap_insert(c.spt, &c.ss->spt_count, NodeDist{root, dv}, &c.ss->oflow);
             }
             __syncthreads();
         } else {
             for (int base = cs; base < ce; base += 64)
-                stage_children<T, DM>(c, base, min(64, ce - base));
+                stage_children<T, DM, DC>(c, base, min(64, ce - base));
         }
     }
 }
@@ -801,7 +825,7 @@ struct PhaseClock {
     }
 };
 
-template <typename T, int DM, bool LDSHEAP, bool PROF = false>
+template <typename T, int DM, int DC, bool LDSHEAP, bool PROF = false>
 __global__ __launch_bounds__(64, SPTAG_LB_WAVES)
 void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
 {
@@ -811,7 +835,7 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     PhaseClock<PROF> clk;
 
     const LdsLayout L = lds_layout(di.dim, sizeof(T), cfg.k, MAX_DEG, cfg.dpq_cap,
-                                   true, LDSHEAP ? cfg.ng_cap : 0);
+                                   true, LDSHEAP ? cfg.ng_lsplit : 0);
     HeapRef ng, spt;
     search_heaps<LDSHEAP>(cfg, bufs, L, q, ng, spt);
     QCtx<T> c = begin_query<T>(&di, &cfg, L, bufs.queries, q, cfg.k, nullptr, ng, spt,
@@ -830,9 +854,9 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     int dlen = 1, dargmax = 0;
 
     clk.mark();
-    init_search_trees_dev<T, DM>(c);
+    init_search_trees_dev<T, DM, DC>(c);
     __syncthreads();
-    search_trees_dev<T, DM>(c, cfg.init_pivots);
+    search_trees_dev<T, DM, DC>(c, cfg.init_pivots);
     clk.acc(0);
 
     int popped = 0;
@@ -891,7 +915,7 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
 
         int ncand = expand_neighbors(c, row);
         clk.acc(4);
-        stage_dists<T, DM>(c, ncand);
+        stage_dists<T, DM, DC>(c, ncand);
         clk.acc(5);
         /* insert phase (BKTIndex.cpp:337-344). m_Results (the flat max-set)
          * appends in O(1); a replace costs one wave-parallel max rescan
@@ -938,7 +962,7 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         __syncthreads();
         clk.acc(6);
         if (ss->want_tree)
-            search_trees_dev<T, DM>(c, cfg.other_pivots + ss->checked);
+            search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked);
         clk.acc(7);
         lookahead_next(c, spec_sink);
         clk.acc(8);
@@ -966,8 +990,11 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
  * results queue, counters) persists in global scratch between calls.
  * ------------------------------------------------------------------ */
 
-template <typename T, int DM>
-__global__ __launch_bounds__(64, SPTAG_LB_WAVES)
+/* The small-class cosine form allocates 81 VGPRs unhinted, one above the
+ * 6 waves/SIMD step; the hint brings it to 80 without scratch (checked in
+ * profiles/occupancy_kernel_resources.txt). */
+template <typename T, int DM, int DC>
+__global__ __launch_bounds__(64, (DC == DC_SMALL && SPTAG_LB_WAVES < 6) ? 6 : SPTAG_LB_WAVES)
 void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
 {
     const int q = blockIdx.x;
@@ -1002,9 +1029,9 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
     QRes* qrs = c.qrs;
 
     if (st.first) {
-        init_search_trees_dev<T, DM>(c);
+        init_search_trees_dev<T, DM, DC>(c);
         __syncthreads();
-        search_trees_dev<T, DM>(c, cfg.init_pivots);
+        search_trees_dev<T, DM, DC>(c, cfg.init_pivots);
     }
 
     int count = 0;
@@ -1037,7 +1064,7 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
             int32_t cs0 = -tn[1], ce0 = tn[2];
             for (int base = cs0; base < ce0; base += 64) {
                 int cnt = min(64, ce0 - base);
-                stage_child_dists<T, DM, false>(c, base, cnt);
+                stage_child_dists<T, DM, DC, false>(c, base, cnt);
                 if (lane == 0) {
                     for (int i = 0; i < cnt; i++) {
                         int32_t tmpNode = c.istage[i];
@@ -1052,7 +1079,7 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
         }
 
         int ncand = expand_neighbors(c, row);
-        stage_dists<T, DM>(c, ncand);
+        stage_dists<T, DM, DC>(c, ncand);
         if (lane == 0) {
             for (int r = 0; r < ncand; r++) {
                 float dv = c.dstage[r];
@@ -1065,7 +1092,7 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
         }
         __syncthreads();
         if (ss->want_tree)
-            search_trees_dev<T, DM>(c, cfg.other_pivots + ss->checked);
+            search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked);
     }
     __syncthreads();
 
@@ -1097,7 +1124,7 @@ struct KdtNode { int32_t left, right, split_dim; float split_value; };
 
 /* KDTree.h:234-271 KDTSearch, iterative; lane 0 descends (serial pointer
  * chase), the wave's first 16-lane group computes the leaf distance. */
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 DEV void kdt_search_node_dev(QCtx<T>& c, int32_t node, float dist_bound)
 {
     const DevIndex& di = *c.di;
@@ -1126,7 +1153,7 @@ DEV void kdt_search_node_dev(QCtx<T>& c, int32_t node, float dist_bound)
     if (index >= 0) {
         float dv = 0.0f;
         if (c.lane < 16)
-            dv = ref_dist_grp<T, DM>(c.qlds, vec_at<T>(di, index), di.dim);
+            dv = ref_dist_grp<T, DM, DC>(c.qlds, vec_at<T>(di, index), di.dim);
         if (c.lane == 0) {
             ss->tree_checked++;
             ss->checked++;
@@ -1137,7 +1164,7 @@ DEV void kdt_search_node_dev(QCtx<T>& c, int32_t node, float dist_bound)
 }
 
 /* KDTree.h:219-231 SearchTrees: pop bounds until the leaf budget. */
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 DEV void kdt_search_trees_dev(QCtx<T>& c, int limits)
 {
     SerialState* ss = c.ss;
@@ -1147,12 +1174,12 @@ DEV void kdt_search_trees_dev(QCtx<T>& c, int limits)
         if (c.lane == 0) ss->popped = ndheap_pop(c.spt, &ss->spt_count);
         __syncthreads();
         NodeDist tcell = ss->popped;
-        kdt_search_node_dev<T, DM>(c, tcell.node, tcell.distance);
+        kdt_search_node_dev<T, DM, DC>(c, tcell.node, tcell.distance);
     }
     __syncthreads();
 }
 
-template <typename T, int DM, bool LDSHEAP>
+template <typename T, int DM, int DC, bool LDSHEAP>
 __global__ __launch_bounds__(64, SPTAG_LB_WAVES)
 void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
 {
@@ -1163,7 +1190,7 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     /* same layout as the BKT kernel; the results-queue region is reserved
      * but unused here (KDT has no results-queue gate) */
     const LdsLayout L = lds_layout(di.dim, sizeof(T), cfg.k, MAX_DEG, cfg.dpq_cap,
-                                   true, LDSHEAP ? cfg.ng_cap : 0);
+                                   true, LDSHEAP ? cfg.ng_lsplit : 0);
     HeapRef ng, spt;
     search_heaps<LDSHEAP>(cfg, bufs, L, q, ng, spt);
     QCtx<T> c = begin_query<T>(&di, &cfg, L, bufs.queries, q, cfg.k, nullptr, ng, spt,
@@ -1173,8 +1200,8 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
 
     /* InitSearchTrees (KDTree.h:213): every tree root at bound 0 */
     for (int t = 0; t < di.ntrees; t++)
-        kdt_search_node_dev<T, DM>(c, di.tree_start[t], 0.0f);
-    kdt_search_trees_dev<T, DM>(c, cfg.init_pivots);
+        kdt_search_node_dev<T, DM, DC>(c, di.tree_start[t], 0.0f);
+    kdt_search_trees_dev<T, DM, DC>(c, cfg.init_pivots);
 
     int popped = 0;
     uint32_t spec_sink = 0;
@@ -1204,7 +1231,7 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         float upper_bound = ss->fbcast;
 
         int ncand = expand_neighbors(c, row);
-        stage_dists<T, DM>(c, ncand);
+        stage_dists<T, DM, DC>(c, ncand);
         if (lane == 0) {
             /* KDTIndex.cpp:211-233: every computed neighbor joins the
              * frontier; track whether any beat the upper bound */
@@ -1229,7 +1256,7 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         __syncthreads();
         if (ss->break_flag) break;
         if (ss->want_tree)
-            kdt_search_trees_dev<T, DM>(c, cfg.other_pivots + ss->checked);
+            kdt_search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked);
         lookahead_next(c, spec_sink);
     }
     __syncthreads();
@@ -1250,7 +1277,7 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
  * One query per wave; test-scale only.
  * ------------------------------------------------------------------ */
 
-template <typename T, int DM>
+template <typename T, int DM, int DC>
 __global__ __launch_bounds__(64)
 void truth_kernel(DevIndex di, const void* queries, int32_t nq, int32_t k,
                   int32_t* out_vids, float* out_dists)
@@ -1269,7 +1296,7 @@ void truth_kernel(DevIndex di, const void* queries, int32_t nq, int32_t k,
         int cnt = min(4, di.n - base);
         int j = lane >> 4;
         if (j < cnt) {
-            float dv = ref_dist_grp<T, DM>(c.qlds, vec_at<T>(di, base + j), di.dim);
+            float dv = ref_dist_grp<T, DM, DC>(c.qlds, vec_at<T>(di, base + j), di.dim);
             if ((lane & 15) == 0) dstage[j] = dv;
         }
         __syncthreads();
@@ -1334,33 +1361,41 @@ int launch_scatter_rows(void* dst, const void* src, int row_bytes,
 
 template <typename T> struct TypeTag { using type = T; };
 
-/* call f(TypeTag<T>, integral_constant<DM>) for the runtime (vt, dm) */
+/* call f(TypeTag<T>, integral_constant<DM>, integral_constant<DC>) for the
+ * runtime (vt, dm, dim); only float has two dimension classes */
 template <typename F>
-static int dispatch_vt_dm(int vt, int dm, F&& f)
+static int dispatch_kernel(int vt, int dm, int dim, F&& f)
 {
     using L2 = std::integral_constant<int, DM_L2>;
     using Cos = std::integral_constant<int, DM_COSINE>;
-    if (vt == VT_FLOAT && dm == DM_L2) return f(TypeTag<float>{}, L2{});
-    if (vt == VT_FLOAT && dm == DM_COSINE) return f(TypeTag<float>{}, Cos{});
-    if (vt == VT_INT8 && dm == DM_L2) return f(TypeTag<int8_t>{}, L2{});
-    if (vt == VT_INT8 && dm == DM_COSINE) return f(TypeTag<int8_t>{}, Cos{});
+    using Small = std::integral_constant<int, DC_SMALL>;
+    using Large = std::integral_constant<int, DC_LARGE>;
+    const bool large = dim > DC_SMALL_MAX_DIM;
+    if (vt == VT_FLOAT && dm == DM_L2)
+        return large ? f(TypeTag<float>{}, L2{}, Large{})
+                     : f(TypeTag<float>{}, L2{}, Small{});
+    if (vt == VT_FLOAT && dm == DM_COSINE)
+        return large ? f(TypeTag<float>{}, Cos{}, Large{})
+                     : f(TypeTag<float>{}, Cos{}, Small{});
+    if (vt == VT_INT8 && dm == DM_L2) return f(TypeTag<int8_t>{}, L2{}, Small{});
+    if (vt == VT_INT8 && dm == DM_COSINE) return f(TypeTag<int8_t>{}, Cos{}, Small{});
     return (int)hipErrorInvalidValue;
 }
 
-template <typename T, int DM, bool LDSHEAP>
+template <typename T, int DM, int DC, bool LDSHEAP>
 static int launch_one(const DevIndex& di, const SearchCfg& cfg,
                       const SearchBufs& bufs, hipStream_t stream)
 {
     size_t lds = lds_bytes(di.dim, sizeof(T), cfg, LDSHEAP);
     dim3 grid(cfg.nq), block(64);
     if (di.algo == ALGO_KDT)
-        hipLaunchKernelGGL((kdt_search_kernel<T, DM, LDSHEAP>), grid, block, lds,
+        hipLaunchKernelGGL((kdt_search_kernel<T, DM, DC, LDSHEAP>), grid, block, lds,
                            stream, di, cfg, bufs);
     else if (cfg.prof)
-        hipLaunchKernelGGL((bkt_search_kernel<T, DM, LDSHEAP, true>), grid,
+        hipLaunchKernelGGL((bkt_search_kernel<T, DM, DC, LDSHEAP, true>), grid,
                            block, lds, stream, di, cfg, bufs);
     else
-        hipLaunchKernelGGL((bkt_search_kernel<T, DM, LDSHEAP, false>), grid,
+        hipLaunchKernelGGL((bkt_search_kernel<T, DM, DC, LDSHEAP, false>), grid,
                            block, lds, stream, di, cfg, bufs);
     return (int)hipGetLastError();
 }
@@ -1368,22 +1403,23 @@ static int launch_one(const DevIndex& di, const SearchCfg& cfg,
 int launch_bkt_search(int vt, int dm, bool heaps_in_lds, const DevIndex& di,
                       const SearchCfg& cfg, const SearchBufs& bufs, void* stream)
 {
-    return dispatch_vt_dm(vt, dm, [&](auto t, auto d) {
+    return dispatch_kernel(vt, dm, di.dim, [&](auto t, auto d, auto c) {
         using T = typename decltype(t)::type;
-        constexpr int DM = decltype(d)::value;
+        constexpr int DM = decltype(d)::value, DC = decltype(c)::value;
         hipStream_t s = (hipStream_t)stream;
-        return heaps_in_lds ? launch_one<T, DM, true>(di, cfg, bufs, s)
-                            : launch_one<T, DM, false>(di, cfg, bufs, s);
+        return heaps_in_lds ? launch_one<T, DM, DC, true>(di, cfg, bufs, s)
+                            : launch_one<T, DM, DC, false>(di, cfg, bufs, s);
     });
 }
 
 int launch_bkt_iter(int vt, int dm, const DevIndex& di, const SearchCfg& cfg,
                     const IterBufs& ib, int batch, void* stream)
 {
-    return dispatch_vt_dm(vt, dm, [&](auto t, auto d) {
+    return dispatch_kernel(vt, dm, di.dim, [&](auto t, auto d, auto c) {
         using T = typename decltype(t)::type;
+        constexpr int DM = decltype(d)::value, DC = decltype(c)::value;
         size_t lds = iter_lds_layout(di.dim, sizeof(T), batch).total;
-        hipLaunchKernelGGL((bkt_iter_kernel<T, decltype(d)::value>), dim3(cfg.nq),
+        hipLaunchKernelGGL((bkt_iter_kernel<T, DM, DC>), dim3(cfg.nq),
                            dim3(64), lds, (hipStream_t)stream, di, cfg, ib, batch);
         return (int)hipGetLastError();
     });
@@ -1392,10 +1428,11 @@ int launch_bkt_iter(int vt, int dm, const DevIndex& di, const SearchCfg& cfg,
 int launch_truth(int vt, int dm, const DevIndex& di, const void* queries,
                  int32_t nq, int32_t k, int32_t* ov, float* od, void* stream)
 {
-    return dispatch_vt_dm(vt, dm, [&](auto t, auto d) {
+    return dispatch_kernel(vt, dm, di.dim, [&](auto t, auto d, auto c) {
         using T = typename decltype(t)::type;
+        constexpr int DM = decltype(d)::value, DC = decltype(c)::value;
         size_t lds = truth_lds_layout(di.dim, sizeof(T), k).total;
-        hipLaunchKernelGGL((truth_kernel<T, decltype(d)::value>), dim3(nq), dim3(64),
+        hipLaunchKernelGGL((truth_kernel<T, DM, DC>), dim3(nq), dim3(64),
                            lds, (hipStream_t)stream, di, queries, nq, k, ov, od);
         return (int)hipGetLastError();
     });
