@@ -183,6 +183,88 @@ DEV int dpq_insert(float* a, int* len, int cap, float dist)
     return 1;
 }
 
+/* v broadcast from lane l (wave-uniform l) */
+DEV float lane_bcast(float v, int l)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+/* DistPriorityQueue (WorkSpace.h:167-225) for one whole adjacency row, wave-
+ * wide. Only the queue's kept multiset and its maximum are observable, so
+ * the batched search keeps it as `cap` floats in LDS, SORTED ascending, with
+ * dmax == dpq[cap-1] replicated in a register. Unfilled slots hold MaxDist:
+ * a queue of len < cap with its MaxDist seed behaves exactly like a full one
+ * padded with MaxDist (an append is a replace of one MaxDist, and the
+ * maximum is MaxDist either way), so there is no length.
+ *
+ * The reference visits candidates r = 0..ncand-1 in row order: if
+ * !(d_r > max(S_r)) it replaces one maximum of S_r by d_r and NG-inserts r.
+ * By induction S_r is the cap smallest of U_r = S0 + {accepted j < r}, so
+ * max(S_r) is U_r's cap-th smallest and
+ *     accept_r  <=>  #{x in U_r : x < d_r} < cap.
+ * A rejected j < r has d_j > max(S_j) >= max(S_r): it is never strictly
+ * below an accepted d_r, and counting it for an r that is rejected anyway
+ * only raises a count already >= cap. So the count may run over S0 and ALL
+ * earlier candidates, which makes it a function of S0 and the row alone:
+ *     accept_r  <=>  #{x in S0 : x < d_r} + #{j < r : d_j < d_r} < cap.
+ * The strict `<` is `dist > a[1] -> reject` on ties. d_r > dmax0 implies
+ * cap elements of S0 below d_r; that gate only skips work.
+ *
+ * Lane r holds d_r (`dv`, lanes >= ncand unused). Returns the accept mask
+ * and leaves the cap smallest of S0 + accepted in dpq, merged by rank: ties
+ * put accepted before S0 and lower lane / lower slot first, so S0 slot i
+ * moves to i + #{a : d_a <= x_i} and accepted a to #{x in S0 : x < d_a} +
+ * #{a' before a}; ranks >= cap fall out. Slots only move up, by at most
+ * popc(acc) <= 64, so 64-slot chunks are rewritten in place top down, and
+ * the accepted, whose ranks may lie in a chunk not read yet, go in last. */
+DEV uint64_t dpq_accept_row(float* dpq, int cap, int ncand, float dv, float& dmax)
+{
+    const int lane = threadIdx.x;
+    const uint64_t gate = __ballot(lane < ncand && !(dv > dmax));
+    if (!gate) return 0;
+
+    int below_row = 0;      /* #{j < lane : d_j < dv} */
+    for (uint64_t m = gate; m; m &= m - 1) {
+        int j = __builtin_ctzll(m);
+        below_row += (j < lane && lane_bcast(dv, j) < dv);
+    }
+    int below_set = 0;      /* #{x in S0 : x < dv} */
+    for (int base = 0; base < cap; base += 64) {
+        float x = base + lane < cap ? dpq[base + lane] : MAXDIST;
+        for (uint64_t m = gate; m; m &= m - 1) {
+            int r = __builtin_ctzll(m);
+            int n = __popcll(__ballot(x < lane_bcast(dv, r)));
+            if (lane == r) below_set += n;
+        }
+    }
+    const uint64_t acc = __ballot(((gate >> lane) & 1) && below_set + below_row < cap);
+    if (!acc) return 0;
+
+    int ra = below_set;     /* rank of this lane's accepted candidate */
+    for (uint64_t m = acc; m; m &= m - 1) {
+        int a = __builtin_ctzll(m);
+        float da = lane_bcast(dv, a);
+        ra += (da < dv || (da == dv && a < lane));
+    }
+    for (int base = (cap - 1) & ~63; base >= 0; base -= 64) {
+        const int i = base + lane;
+        float x = i < cap ? dpq[i] : MAXDIST;
+        int rx = i;
+        for (uint64_t m = acc; m; m &= m - 1)
+            rx += (lane_bcast(dv, __builtin_ctzll(m)) <= x);
+        /* sorted: a chunk that stays put is below every accepted value,
+         * and so is everything under it */
+        if (!__ballot(i < cap && rx != i)) break;
+        __syncthreads();
+        if (i < cap && rx < cap) dpq[rx] = x;
+    }
+    __syncthreads();
+    if (((acc >> lane) & 1) && ra < cap) dpq[ra] = dv;
+    __syncthreads();
+    dmax = dpq[cap - 1];
+    return acc;
+}
+
 /* QueryResultSet (QueryResultSet.h:17-120): 0-based k-entry max-heap on
  * (dist, vid). */
 DEV int qres_lt(QRes x, QRes y)
@@ -600,22 +682,22 @@ DEV void stage_dists(QCtx<T>& c, int cnt)
     __syncthreads();
 }
 
-/* Warm the GLOBAL parent-chain levels of the next `cnt` SPT insertion
- * slots (slot for the i-th insert is spt_count+1+i while the heap is not
- * full — seed-phase heaps never reach ref_cap in practice, and the warm is
- * advisory: a wrong slot guess only wastes a touch). Lane-0's serial
- * percolate-up then reads L1/L2-warm lines instead of paying an HBM
- * round trip per level — the seed phase was 31% of kernel cycles with
- * cold parent reads. */
-template <typename T>
-DEV void spt_warm_parents(QCtx<T>& c, int cnt)
+/* Warm the GLOBAL parent-chain levels of the next `cnt` (<= 64) insertion
+ * slots of heap `h` holding `count` entries (slot for the i-th insert is
+ * count+1+i while the heap is not full, and the warm is advisory: a wrong
+ * slot guess only wastes a touch; slots past the capacity are not guessed).
+ * Lane-0's serial percolate-up then reads L1/L2-warm lines instead of
+ * paying an HBM round trip per level — the seed phase was 31% of kernel
+ * cycles with cold SPT parent reads. Levels in the LDS tier are skipped. */
+DEV void heap_warm_parents(const HeapRef& h, int count, int cnt)
 {
-    int loc = c.ss->spt_count + 1 + c.lane;
+    const int lane = threadIdx.x;
+    int loc = count + 1 + lane;
     uint32_t wsink = 0;
-    if (c.lane < cnt) {
+    if (lane < cnt && loc <= h.cap && h.a) {
         int par = loc >> 1;
-        while (par > c.spt.lsplit) {
-            wsink += ((const uint8_t*)&c.spt.a[par])[0];
+        while (par > h.lsplit) {
+            wsink += ((const uint8_t*)&h.a[par])[0];
             par >>= 1;
         }
     }
@@ -645,7 +727,7 @@ template <typename T, int DM, int DC>
 DEV void stage_children(QCtx<T>& c, int base, int cnt)
 {
     stage_child_dists<T, DM, DC, true>(c, base, cnt);
-    spt_warm_parents(c, cnt);
+    heap_warm_parents(c.spt, c.ss->spt_count, cnt);
     if (c.lane == 0)
         for (int i = 0; i < cnt; i++)
             ndheap_insert(c.spt, &c.ss->spt_count,
@@ -844,14 +926,11 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     QRes* qrs = c.qrs;
     float* dpq = c.dpq;
 
-    /* DistPriorityQueue (WorkSpace.h:167-225) as a FLAT bounded max-set:
-     * its observable behavior (the kept multiset and its current maximum)
-     * is independent of heap layout, so the m_Results state here is an
-     * unordered LDS array + uniform registers replicated wave-wide; slot 0
-     * starts as the queue's MaxDist seed element. */
-    if (lane == 0) dpq[0] = MAXDIST;
+    /* m_Results: the sorted LDS set of dpq_accept_row, the queue's MaxDist
+     * seed and its unfilled slots alike as MaxDist; published by the
+     * barriers of the seed phase. */
+    for (int i = lane; i < cfg.dpq_cap; i += 64) dpq[i] = MAXDIST;
     float dmax = MAXDIST;
-    int dlen = 1, dargmax = 0;
 
     clk.mark();
     init_search_trees_dev<T, DM, DC>(c);
@@ -917,44 +996,25 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         clk.acc(4);
         stage_dists<T, DM, DC>(c, ncand);
         clk.acc(5);
-        /* insert phase (BKTIndex.cpp:337-344). m_Results (the flat max-set)
-         * appends in O(1); a replace costs one wave-parallel max rescan
-         * (any max-valued slot may be replaced — same multiset). The NG
-         * frontier heap stays an exact Heap.h emulation on lane 0: its pop
-         * order on equal keys is part of the parity contract. */
-        for (int r = 0; r < ncand; r++) {
-            float dv = c.dstage[r];
-            if (lane == 0) ss->checked++;
-            if (!(dv > dmax)) {
-                if (dlen < cfg.dpq_cap) {
-                    if (lane == 0) dpq[dlen] = dv;
-                    dlen++;
-                } else {
-                    if (lane == 0) dpq[dargmax] = dv;
-                    __syncthreads();
-                    float m = -MAXDIST;
-                    int mi = 0;
-                    for (int i = lane; i < cfg.dpq_cap; i += 64) {
-                        float x = dpq[i];
-                        if (x > m) { m = x; mi = i; }
-                    }
-                    for (int o2 = 32; o2 > 0; o2 >>= 1) {
-                        float om = __shfl_down(m, o2);
-                        int omi = __shfl_down(mi, o2);
-                        if (om > m) { m = om; mi = omi; }
-                    }
-                    dmax = __shfl(m, 0);
-                    dargmax = __shfl(mi, 0);
-                }
-                if (lane == 0) {
-                    clk.ng_begin();
-                    ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], dv},
-                                  &ss->oflow);
-                    clk.ng_end();
-                }
-            }
-        }
+        /* insert phase (BKTIndex.cpp:337-344). Which of the row's
+         * candidates m_Results accepts is decided once, wave-wide, from the
+         * set at the start of the pop (dpq_accept_row); nothing between two
+         * NG inserts depends on the set any more. The NG frontier heap stays
+         * an exact Heap.h emulation on lane 0 (its pop order on equal keys
+         * is part of the parity contract): the accepted candidates go in
+         * row order, back to back. Nothing reads `checked` inside a row. */
+        const uint64_t acc = dpq_accept_row(
+            dpq, cfg.dpq_cap, ncand, lane < ncand ? c.dstage[lane] : MAXDIST, dmax);
+        heap_warm_parents(c.ng, ss->ng_count, __popcll(acc));
         if (lane == 0) {
+            ss->checked += ncand;
+            clk.ng_begin();
+            for (uint64_t m = acc; m; m &= m - 1) {
+                int r = __builtin_ctzll(m);
+                ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], c.dstage[r]},
+                              &ss->oflow);
+            }
+            clk.ng_end();
             /* dynamic pivots (BKTIndex.cpp:346-349) */
             ss->want_tree = (ndheap_top(c.ng, ss->ng_count).distance >
                              ndheap_top(c.spt, ss->spt_count).distance);
