@@ -27,6 +27,10 @@
  *   sptag_amd_save_index    <- VectorIndex::SaveIndex(folder)
  *                              (inc/Core/VectorIndex.h:87): writes the same
  *                              byte format the reference loads.
+ *   sptag_amd_shards_*      <- AggregatorService::AggregateResults
+ *                              (src/Aggregator/AggregatorService.cpp:363):
+ *                              per-shard lists concatenated, top k selected;
+ *                              here inside one process, merged on the GPU.
  *
  * All device state lives behind the opaque handle. Errors are negative int
  * codes; no exceptions cross this boundary. Thread-safety: search is
@@ -171,6 +175,81 @@ void sptag_amd_set_search_params(SptagAmdIndex* idx, int32_t init_pivots,
                                  int32_t other_pivots,
                                  int32_t nobetter_threshold,
                                  int32_t default_maxcheck);
+
+/* Shard sets — several indexes searched as one, the per-shard top-k lists
+ * merged on the GPU. This is the in-process form of the reference's
+ * aggregator, AggregatorService::AggregateResults
+ * (src/Aggregator/AggregatorService.cpp:363): every shard answers the whole
+ * query batch, the lists are concatenated and the best k selected. The
+ * result contract is the single index's, over global ids: ascending
+ * (dist, global vid) with global vid = shard-local vid + vid_base[shard],
+ * then vid = -1 padding that carries the padding distance of the
+ * single-index search. Ties between shards are therefore decided by global
+ * id, exactly as ties inside one index are decided by id.
+ *
+ * Merge utility, usable without a shard set (e.g. on lists gathered from
+ * other processes). vids/dists are [nshards][nq][k_in]; every list is
+ * ascending (dist, vid) and its padding is a suffix of vid < 0 entries. The
+ * outputs are [nq][k_out] and must not overlap the inputs; k_out may exceed
+ * nshards*k_in, the surplus is padding. 1 <= nshards <= 64,
+ * 1 <= k_in, k_out <= 1024, every vid_base[s] >= 0; vid_base is always a
+ * host array. The _device form takes buffers on GPU `device`, runs on that
+ * device's default stream and returns when the output is complete. */
+int sptag_amd_merge_topk_device(int device, int32_t nshards, int32_t nq,
+                                int32_t k_in, int32_t k_out,
+                                const int32_t* d_vids, const float* d_dists,
+                                const int32_t* vid_base,
+                                int32_t* d_out_vids, float* d_out_dists);
+int sptag_amd_merge_topk(int device, int32_t nshards, int32_t nq,
+                         int32_t k_in, int32_t k_out,
+                         const int32_t* vids, const float* dists,
+                         const int32_t* vid_base,
+                         int32_t* out_vids, float* out_dists);
+
+/* A set of 1..64 shards that agree in dim, value type and distance method;
+ * BKT and KDT shards may be mixed, and the shards may sit on one device or
+ * on several. vid_base[s] is the global id of shard s's vector 0; NULL
+ * means the running sum of the shards' vector counts at create time.
+ * Returns NULL, with a line on stderr, when nshards is out of range, a
+ * shard is NULL, the shards disagree, or some vid_base[s] + num_vectors(s)
+ * does not fit int32.
+ *
+ * The set borrows the handles: it never frees them, and they must outlive
+ * it. Add and delete stay on the shard handles and a set sees them on its
+ * next call. vid_base is fixed at create time, so vectors added to any
+ * shard but the last run into the next shard's ids under the default bases:
+ * a set whose shards will grow needs explicit bases that leave room.
+ * Iterators over a set are not provided. */
+typedef struct SptagAmdShards SptagAmdShards;
+SptagAmdShards* sptag_amd_shards_create(SptagAmdIndex* const* shards,
+                                        int32_t nshards,
+                                        const int32_t* vid_base);
+void sptag_amd_shards_free(SptagAmdShards* set);
+
+/* Batched search of the whole set; arguments and result layout as in the
+ * single-index search, ids global. Shards on one device run one after
+ * another in the calling thread; with more than one device there is one
+ * host thread per device, and queries and lists travel between devices by
+ * hipMemcpyPeer (peer access is not required). The merge runs on the device
+ * of shard 0. A failing shard's error code is returned and the outputs are
+ * left untouched. Concurrent callers on one set are serialized. */
+int sptag_amd_shards_search_batch(SptagAmdShards* set, const void* queries,
+                                  int32_t nq, int32_t k, int32_t max_check,
+                                  int32_t* out_vids, float* out_dists);
+/* Device-pointer variant: all three buffers on the device of shard 0. */
+int sptag_amd_shards_search_batch_device(SptagAmdShards* set,
+                                         const void* d_queries, int32_t nq,
+                                         int32_t k, int32_t max_check,
+                                         int32_t* d_out_vids,
+                                         float* d_out_dists);
+/* Exact brute-force top-k over all shards: the same fan-out over the
+ * per-shard truth, the same merge. Host pointers. */
+int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries,
+                           int32_t nq, int32_t k, int32_t* out_vids,
+                           float* out_dists);
+int32_t sptag_amd_shards_count(const SptagAmdShards* set);
+/* sum of the shards' current vector counts */
+int64_t sptag_amd_shards_num_vectors(const SptagAmdShards* set);
 
 /* metadata */
 int32_t sptag_amd_num_vectors(const SptagAmdIndex* idx);

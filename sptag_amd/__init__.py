@@ -15,8 +15,8 @@ import os
 
 import numpy as np
 
-__all__ = ["AnnIndex", "MetadataSet", "load_library", "gpu_available",
-           "SptagAmdError"]
+__all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "MetadataSet",
+           "load_library", "gpu_available", "SptagAmdError"]
 
 _LIB = None
 _LIBPATH = os.environ.get(
@@ -101,6 +101,28 @@ def load_library():
     lib.sptag_amd_set_search_params.argtypes = [
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
         ctypes.c_int32]
+    lib.sptag_amd_merge_topk.restype = ctypes.c_int
+    lib.sptag_amd_merge_topk.argtypes = [
+        ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p]
+    lib.sptag_amd_merge_topk_device.restype = ctypes.c_int
+    lib.sptag_amd_merge_topk_device.argtypes = lib.sptag_amd_merge_topk.argtypes
+    lib.sptag_amd_shards_create.restype = ctypes.c_void_p
+    lib.sptag_amd_shards_create.argtypes = [ctypes.c_void_p, ctypes.c_int32,
+                                            ctypes.c_void_p]
+    lib.sptag_amd_shards_free.argtypes = [ctypes.c_void_p]
+    lib.sptag_amd_shards_search_batch.restype = ctypes.c_int
+    lib.sptag_amd_shards_search_batch.argtypes = lib.sptag_amd_search_batch.argtypes
+    lib.sptag_amd_shards_search_batch_device.restype = ctypes.c_int
+    lib.sptag_amd_shards_search_batch_device.argtypes = \
+        lib.sptag_amd_search_batch.argtypes
+    lib.sptag_amd_shards_truth.restype = ctypes.c_int
+    lib.sptag_amd_shards_truth.argtypes = lib.sptag_amd_truth.argtypes
+    lib.sptag_amd_shards_count.restype = ctypes.c_int32
+    lib.sptag_amd_shards_count.argtypes = [ctypes.c_void_p]
+    lib.sptag_amd_shards_num_vectors.restype = ctypes.c_int64
+    lib.sptag_amd_shards_num_vectors.argtypes = [ctypes.c_void_p]
     lib.sptag_amd_gpu_available.restype = ctypes.c_int
     lib.sptag_amd_build_info.restype = ctypes.c_char_p
     _LIB = lib
@@ -343,6 +365,116 @@ class AnnIndex:
         rc = self._lib.sptag_amd_save_index(self._h, str(folder).encode())
         if rc != 0:
             raise SptagAmdError(rc, "save_index")
+
+
+def merge_topk(vids, dists, vid_base, k, device=0):
+    """Merge per-shard top-k lists on the GPU (reference AggregatorService::
+    AggregateResults, AggregatorService.cpp:363). vids int32 / dists float32
+    of shape [S, nq, k_in], every list ascending (dist, vid) with its padding
+    a suffix of vid < 0; vid_base [S] is added to the ids of shard s. Returns
+    (vids [nq,k], dists [nq,k]) ascending (dist, global vid), vid=-1 padding."""
+    vids = np.ascontiguousarray(vids, dtype=np.int32)
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    vid_base = np.ascontiguousarray(vid_base, dtype=np.int32)
+    if vids.ndim != 3 or dists.shape != vids.shape:
+        raise ValueError("vids and dists must both be [S, nq, k_in]")
+    nshards, nq, k_in = vids.shape
+    if vid_base.shape != (nshards,):
+        raise ValueError(f"vid_base must hold {nshards} values")
+    out_v = np.empty((nq, k), dtype=np.int32)
+    out_d = np.empty((nq, k), dtype=np.float32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    rc = load_library().sptag_amd_merge_topk(
+        device, nshards, nq, k_in, k, p(vids), p(dists), p(vid_base),
+        p(out_v), p(out_d))
+    if rc != 0:
+        raise SptagAmdError(rc, "merge_topk")
+    return out_v, out_d
+
+
+class ShardedIndex:
+    """Several AnnIndex shards searched as one: every shard answers the whole
+    batch and the lists are merged on the GPU of shard 0, ascending (dist,
+    global vid) with global vid = shard vid + vid_base[shard]. Add and Delete
+    stay on the shards' own AnnIndex objects (`.shards`); the set sees them
+    on its next call."""
+
+    def __init__(self, handle, shards):
+        self._lib = load_library()
+        self._h = handle
+        self.shards = list(shards)   # the C set borrows their handles
+        if not handle:
+            raise SptagAmdError(-2, "shards_create refused (see stderr)")
+
+    @classmethod
+    def FromIndexes(cls, indexes, vid_base=None):
+        """vid_base None = running sum of the shards' sizes now; give
+        explicit bases with room if shards other than the last will grow."""
+        indexes = list(indexes)
+        lib = load_library()
+        handles = (ctypes.c_void_p * len(indexes))(*[ix._h for ix in indexes])
+        basep = None
+        if vid_base is not None:
+            vid_base = np.ascontiguousarray(vid_base, dtype=np.int32)
+            if vid_base.shape != (len(indexes),):
+                raise ValueError(f"vid_base must hold {len(indexes)} values")
+            basep = vid_base.ctypes.data_as(ctypes.c_void_p)
+        return cls(lib.sptag_amd_shards_create(handles, len(indexes), basep),
+                   indexes)
+
+    @classmethod
+    def Load(cls, folders, devices=None):
+        """One index folder per shard; devices[i] is shard i's GPU
+        (default: all on device 0)."""
+        folders = list(folders)
+        if devices is None:
+            devices = [0] * len(folders)
+        if len(devices) != len(folders):
+            raise ValueError("one device per folder")
+        return cls.FromIndexes([AnnIndex.Load(f, d)
+                                for f, d in zip(folders, devices)])
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.sptag_amd_shards_free(self._h)
+            self._h = None
+
+    def NumShards(self):
+        return self._lib.sptag_amd_shards_count(self._h)
+
+    def NumVectors(self):
+        return self._lib.sptag_amd_shards_num_vectors(self._h)
+
+    def _call(self, fn, what, queries, k, *mid):
+        queries = self.shards[0]._rows(queries)
+        nq = queries.shape[0]
+        vids = np.empty((nq, k), dtype=np.int32)
+        dists = np.empty((nq, k), dtype=np.float32)
+        rc = fn(self._h, queries.ctypes.data_as(ctypes.c_void_p), nq, k, *mid,
+                vids.ctypes.data_as(ctypes.c_void_p),
+                dists.ctypes.data_as(ctypes.c_void_p))
+        if rc != 0:
+            raise SptagAmdError(rc, what)
+        return vids, dists
+
+    def BatchSearch(self, queries, k, max_check=0):
+        """(vids int32 [nq,k], dists f32 [nq,k]) over all shards, global ids."""
+        return self._call(self._lib.sptag_amd_shards_search_batch,
+                          "shards_search_batch", queries, k, max_check)
+
+    def BatchSearchDevice(self, d_queries_ptr, nq, k, d_vids_ptr, d_dists_ptr,
+                          max_check=0):
+        """All pointers are HIP device addresses on the device of shard 0."""
+        rc = self._lib.sptag_amd_shards_search_batch_device(
+            self._h, ctypes.c_void_p(d_queries_ptr), nq, k, max_check,
+            ctypes.c_void_p(d_vids_ptr), ctypes.c_void_p(d_dists_ptr))
+        if rc != 0:
+            raise SptagAmdError(rc, "shards_search_batch_device")
+
+    def Truth(self, queries, k):
+        """Exact brute-force top-k over all shards, global ids."""
+        return self._call(self._lib.sptag_amd_shards_truth, "shards_truth",
+                          queries, k)
 
 
 class MetadataSet:

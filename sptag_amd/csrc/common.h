@@ -179,4 +179,19 @@ int launch_truth(int valuetype, int distmethod, const DevIndex& di,
                  const void* queries, int32_t nq, int32_t k,
                  int32_t* out_vids, float* out_dists, void* stream);
 
+/* shard merge: at most MAX_SHARDS lists per query; the lists of one query
+ * are staged in LDS up to MERGE_LDS_ENTRIES entries of 8 bytes (32 KiB) */
+enum { MAX_SHARDS = 64, MERGE_LDS_ENTRIES = 4096 };
+
+/* global id of a shard's vector 0, per shard; passed to the kernel by value */
+struct MergeBases { int32_t b[MAX_SHARDS]; };
+
+/* vids/dists: [nshards][nq][k_in] on the current device, each list ascending
+ * (dist, vid) with a vid < 0 padding suffix; out: [nq][k_out], which must
+ * not overlap the inputs */
+int launch_merge_topk(const int32_t* vids, const float* dists,
+                      const MergeBases& bases, int nshards, int32_t nq,
+                      int32_t k_in, int32_t k_out, int32_t* out_vids,
+                      float* out_dists, void* stream);
+
 }  /* namespace sptag_amd */

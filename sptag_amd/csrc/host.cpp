@@ -28,6 +28,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "common.h"
@@ -1299,6 +1300,320 @@ void sptag_amd_set_search_params(SptagAmdIndex* ix, int32_t init_pivots,
     if (other_pivots > 0) ix->other_pivots = other_pivots;
     if (nobetter_threshold > 0) ix->nobetter_threshold = nobetter_threshold;
     if (default_maxcheck > 0) ix->default_maxcheck = default_maxcheck;
+}
+
+}  /* extern "C" */
+
+/* ------------------------------------------------------------------ *
+ * shard sets: several indexes searched as one, merged on the GPU
+ * (reference AggregatorService::AggregateResults,
+ * src/Aggregator/AggregatorService.cpp:363)
+ * ------------------------------------------------------------------ */
+
+/* the shards of one device, and what the set keeps there for them */
+struct ShardGroup {
+    int device = 0;
+    std::vector<int> ids;   /* shard numbers, ascending */
+    DevBuf d_q;             /* the query batch, on devices other than shard 0's */
+    DevBuf d_v, d_d;        /* these shards' lists, likewise: [ids.size()][nq][k] */
+};
+
+struct SptagAmdShards {
+    std::vector<SptagAmdIndex*> shards;   /* not owned */
+    MergeBases bases;
+    std::vector<ShardGroup> groups;       /* groups[0] holds shard 0 */
+    std::mutex lock;                      /* the buffers below serve one call at a time */
+    DevBuf d_allv, d_alld;                /* [S][nq][k] on the device of shard 0 */
+};
+
+/* Run fn(group) for every device group: in the calling thread when all
+ * shards share a device, else one thread per device, each of which selects
+ * its device first. Returns the first group's error, in group order. */
+template <class F>
+static int for_each_group(SptagAmdShards* set, F&& fn)
+{
+    std::vector<int> rc(set->groups.size(), SPTAG_AMD_OK);
+    auto run = [&](size_t g) {
+        if (hipSetDevice(set->groups[g].device) != hipSuccess) {
+            rc[g] = SPTAG_AMD_ERR_NOGPU;
+            return;
+        }
+        rc[g] = fn(set->groups[g]);
+    };
+    if (set->groups.size() == 1) {
+        run(0);
+    } else {
+        std::vector<std::thread> th;
+        for (size_t g = 0; g < set->groups.size(); g++) th.emplace_back(run, g);
+        for (auto& t : th) t.join();
+    }
+    for (int r : rc)
+        if (r != SPTAG_AMD_OK) return r;
+    return SPTAG_AMD_OK;
+}
+
+static int check_shards_args(SptagAmdShards* set, const void* q, int32_t nq, int32_t k)
+{
+    if (!set || !q || nq <= 0 || k <= 0 || k > MAX_K) return SPTAG_AMD_ERR_PARAM;
+    bool resident = sptag_amd_gpu_available();
+    for (SptagAmdIndex* ix : set->shards) resident = resident && ix->d_vectors;
+    if (!resident) {
+        fprintf(stderr,
+                "sptag_amd: shard search requires a HIP device (%s); no CPU fallback\n",
+                sptag_amd_build_info());
+        return SPTAG_AMD_ERR_NOGPU;
+    }
+    return SPTAG_AMD_OK;
+}
+
+static int merge_args_ok(int32_t nshards, int32_t nq, int32_t k_in, int32_t k_out,
+                         const void* vids, const void* dists, const int32_t* vid_base,
+                         const void* out_vids, const void* out_dists)
+{
+    if (nshards < 1 || nshards > MAX_SHARDS || nq <= 0 || k_in <= 0 || k_in > MAX_K ||
+        k_out <= 0 || k_out > MAX_K || !vids || !dists || !vid_base || !out_vids ||
+        !out_dists)
+        return SPTAG_AMD_ERR_PARAM;
+    for (int32_t s = 0; s < nshards; s++)
+        if (vid_base[s] < 0) return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) {
+        fprintf(stderr, "sptag_amd: merge_topk requires a HIP device\n");
+        return SPTAG_AMD_ERR_NOGPU;
+    }
+    return SPTAG_AMD_OK;
+}
+
+/* merge on the current device; returns once the output is complete */
+static int merge_on_device(const MergeBases& bases, int32_t nshards, int32_t nq,
+                           int32_t k_in, int32_t k_out, const int32_t* d_vids,
+                           const float* d_dists, int32_t* d_out_vids, float* d_out_dists)
+{
+    int err = launch_merge_topk(d_vids, d_dists, bases, nshards, nq, k_in, k_out,
+                                d_out_vids, d_out_dists, nullptr);
+    if (err != 0) {
+        fprintf(stderr, "sptag_amd: merge launch failed %d\n", err);
+        return SPTAG_AMD_ERR_INTERNAL;
+    }
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+/* Search every shard into set->d_allv/d_alld ([S][nq][k] on the device of
+ * shard 0, the current device on return). d_q is on that device. */
+static int shards_fan_out_search(SptagAmdShards* set, const void* d_q, int32_t nq,
+                                 int32_t k, int32_t max_check)
+{
+    const int S = (int)set->shards.size();
+    const int dev0 = set->groups[0].device;
+    const size_t list = (size_t)nq * k;          /* entries of one shard's lists */
+    const size_t qbytes = (size_t)nq * set->shards[0]->dim * set->shards[0]->esz();
+    HIP_OR_FAIL(hipSetDevice(dev0), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(set->d_allv.ensure((size_t)S * list * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(set->d_alld.ensure((size_t)S * list * 4), SPTAG_AMD_ERR_OOM);
+    int32_t* allv = set->d_allv.as<int32_t>();
+    float* alld = set->d_alld.as<float>();
+
+    int rc = for_each_group(set, [&](ShardGroup& g) -> int {
+        const bool home = g.device == dev0;
+        const void* q = d_q;
+        if (!home) {
+            HIP_OR_FAIL(g.d_q.ensure(qbytes), SPTAG_AMD_ERR_OOM);
+            HIP_OR_FAIL(g.d_v.ensure(g.ids.size() * list * 4), SPTAG_AMD_ERR_OOM);
+            HIP_OR_FAIL(g.d_d.ensure(g.ids.size() * list * 4), SPTAG_AMD_ERR_OOM);
+            HIP_OR_FAIL(hipMemcpyPeer(g.d_q.as(), g.device, d_q, dev0, qbytes),
+                        SPTAG_AMD_ERR_NOGPU);
+            q = g.d_q.as();
+        }
+        for (size_t j = 0; j < g.ids.size(); j++) {
+            const int s = g.ids[j];
+            SptagAmdIndex* ix = set->shards[s];
+            int32_t* v = home ? allv + s * list : g.d_v.as<int32_t>() + j * list;
+            float* d = home ? alld + s * list : g.d_d.as<float>() + j * list;
+            int r;
+            {
+                std::lock_guard<std::mutex> lk(ix->lock);
+                r = search_device_core(ix, q, nq, k, max_check, v, d);
+            }
+            if (r != SPTAG_AMD_OK) return r;
+            if (!home) {
+                /* staged through the host where the devices are not peers */
+                HIP_OR_FAIL(hipMemcpyPeer(allv + s * list, dev0, v, g.device, list * 4),
+                            SPTAG_AMD_ERR_NOGPU);
+                HIP_OR_FAIL(hipMemcpyPeer(alld + s * list, dev0, d, g.device, list * 4),
+                            SPTAG_AMD_ERR_NOGPU);
+            }
+        }
+        return SPTAG_AMD_OK;
+    });
+    HIP_OR_FAIL(hipSetDevice(dev0), SPTAG_AMD_ERR_NOGPU);
+    return rc;
+}
+
+extern "C" {
+
+int sptag_amd_merge_topk_device(int device, int32_t nshards, int32_t nq, int32_t k_in,
+                                int32_t k_out, const int32_t* d_vids,
+                                const float* d_dists, const int32_t* vid_base,
+                                int32_t* d_out_vids, float* d_out_dists)
+{
+    int rc = merge_args_ok(nshards, nq, k_in, k_out, d_vids, d_dists, vid_base,
+                           d_out_vids, d_out_dists);
+    if (rc != SPTAG_AMD_OK) return rc;
+    MergeBases bases = {};
+    std::copy(vid_base, vid_base + nshards, bases.b);
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    return merge_on_device(bases, nshards, nq, k_in, k_out, d_vids, d_dists,
+                           d_out_vids, d_out_dists);
+}
+
+int sptag_amd_merge_topk(int device, int32_t nshards, int32_t nq, int32_t k_in,
+                         int32_t k_out, const int32_t* vids, const float* dists,
+                         const int32_t* vid_base, int32_t* out_vids, float* out_dists)
+{
+    int rc = merge_args_ok(nshards, nq, k_in, k_out, vids, dists, vid_base, out_vids,
+                           out_dists);
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    const size_t ibytes = (size_t)nshards * nq * k_in * 4, obytes = (size_t)nq * k_out * 4;
+    DevBuf d_v, d_d, d_ov, d_od;
+    if ((rc = dev_upload(d_v, vids, ibytes)) != SPTAG_AMD_OK) return rc;
+    if ((rc = dev_upload(d_d, dists, ibytes)) != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(d_ov.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_od.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    rc = sptag_amd_merge_topk_device(device, nshards, nq, k_in, k_out,
+                                     d_v.as<int32_t>(), d_d.as<float>(), vid_base,
+                                     d_ov.as<int32_t>(), d_od.as<float>());
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(hipMemcpy(out_vids, d_ov.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_dists, d_od.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+SptagAmdShards* sptag_amd_shards_create(SptagAmdIndex* const* shards, int32_t nshards,
+                                        const int32_t* vid_base)
+{
+    if (nshards < 1 || nshards > MAX_SHARDS || !shards) {
+        fprintf(stderr, "sptag_amd: a shard set holds 1..%d shards, got %d\n",
+                (int)MAX_SHARDS, nshards);
+        return nullptr;
+    }
+    std::unique_ptr<SptagAmdShards> set(new SptagAmdShards());
+    set->bases = MergeBases{};
+    int64_t next = 0;   /* running sum of num_vectors */
+    for (int32_t s = 0; s < nshards; s++) {
+        const SptagAmdIndex* ix = shards[s];
+        if (!ix) {
+            fprintf(stderr, "sptag_amd: shard %d is NULL\n", s);
+            return nullptr;
+        }
+        const SptagAmdIndex* first = shards[0];
+        if (ix->dim != first->dim || ix->vt != first->vt || ix->dm != first->dm) {
+            fprintf(stderr, "sptag_amd: shard %d differs from shard 0 in dim, value "
+                            "type or distance method\n", s);
+            return nullptr;
+        }
+        const int64_t base = vid_base ? vid_base[s] : next;
+        if (base < 0 || base + ix->n > (int64_t)INT32_MAX) {
+            fprintf(stderr, "sptag_amd: shard %d: base %lld + %d vectors does not fit "
+                            "int32\n", s, (long long)base, ix->n);
+            return nullptr;
+        }
+        set->bases.b[s] = (int32_t)base;
+        next = base + ix->n;
+        set->shards.push_back(shards[s]);
+        /* shard 0 opens group 0, so that is the merge device's group */
+        auto g = std::find_if(set->groups.begin(), set->groups.end(),
+                              [&](const ShardGroup& x) { return x.device == ix->device; });
+        if (g == set->groups.end()) {
+            set->groups.emplace_back();
+            g = set->groups.end() - 1;
+            g->device = ix->device;
+        }
+        g->ids.push_back(s);
+    }
+    return set.release();
+}
+
+void sptag_amd_shards_free(SptagAmdShards* set)
+{
+    if (set) delete set;   /* the set's own buffers only; the shards stay */
+}
+
+int32_t sptag_amd_shards_count(const SptagAmdShards* set)
+{
+    return set ? (int32_t)set->shards.size() : -1;
+}
+
+int64_t sptag_amd_shards_num_vectors(const SptagAmdShards* set)
+{
+    if (!set) return -1;
+    int64_t n = 0;
+    for (const SptagAmdIndex* ix : set->shards) n += ix->n;
+    return n;
+}
+
+int sptag_amd_shards_search_batch_device(SptagAmdShards* set, const void* d_queries,
+                                         int32_t nq, int32_t k, int32_t max_check,
+                                         int32_t* d_out_vids, float* d_out_dists)
+{
+    int rc = check_shards_args(set, d_queries, nq, k);
+    if (rc != SPTAG_AMD_OK) return rc;
+    if (!d_out_vids || !d_out_dists) return SPTAG_AMD_ERR_PARAM;
+    std::lock_guard<std::mutex> g(set->lock);
+    rc = shards_fan_out_search(set, d_queries, nq, k, max_check);
+    if (rc != SPTAG_AMD_OK) return rc;
+    return merge_on_device(set->bases, (int32_t)set->shards.size(), nq, k, k,
+                           set->d_allv.as<int32_t>(), set->d_alld.as<float>(),
+                           d_out_vids, d_out_dists);
+}
+
+int sptag_amd_shards_search_batch(SptagAmdShards* set, const void* queries, int32_t nq,
+                                  int32_t k, int32_t max_check, int32_t* out_vids,
+                                  float* out_dists)
+{
+    int rc = check_shards_args(set, queries, nq, k);
+    if (rc != SPTAG_AMD_OK) return rc;
+    if (!out_vids || !out_dists) return SPTAG_AMD_ERR_PARAM;
+    HIP_OR_FAIL(hipSetDevice(set->groups[0].device), SPTAG_AMD_ERR_NOGPU);
+    const SptagAmdIndex* ix0 = set->shards[0];
+    const size_t qbytes = (size_t)nq * ix0->dim * ix0->esz(), obytes = (size_t)nq * k * 4;
+    DevBuf d_q, d_v, d_d;
+    if ((rc = dev_upload(d_q, queries, qbytes)) != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(d_v.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_d.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    rc = sptag_amd_shards_search_batch_device(set, d_q.as(), nq, k, max_check,
+                                              d_v.as<int32_t>(), d_d.as<float>());
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(hipMemcpy(out_vids, d_v.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_dists, d_d.as(), obytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries, int32_t nq,
+                           int32_t k, int32_t* out_vids, float* out_dists)
+{
+    int rc = check_shards_args(set, queries, nq, k);
+    if (rc != SPTAG_AMD_OK) return rc;
+    if (!out_vids || !out_dists) return SPTAG_AMD_ERR_PARAM;
+    const int S = (int)set->shards.size();
+    const size_t list = (size_t)nq * k;
+    std::vector<int32_t> hv((size_t)S * list);
+    std::vector<float> hd((size_t)S * list);
+    rc = for_each_group(set, [&](ShardGroup& g) -> int {
+        for (int s : g.ids) {
+            int r = sptag_amd_truth(set->shards[s], queries, nq, k,
+                                    hv.data() + s * list, hd.data() + s * list);
+            if (r != SPTAG_AMD_OK) return r;
+        }
+        return SPTAG_AMD_OK;
+    });
+    if (rc != SPTAG_AMD_OK) return rc;
+    return sptag_amd_merge_topk(set->groups[0].device, S, nq, k, k, hv.data(),
+                                hd.data(), set->bases.b, out_vids, out_dists);
 }
 
 }  /* extern "C" */

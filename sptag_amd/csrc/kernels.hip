@@ -1416,6 +1416,138 @@ int launch_scatter_rows(void* dst, const void* src, int row_bytes,
 }
 
 /* ------------------------------------------------------------------ *
+ * shard merge (AggregatorService::AggregateResults semantics,
+ * src/Aggregator/AggregatorService.cpp:363: concatenate the per-shard
+ * lists, then select): S lists of k_in entries per query, each ascending
+ * by (dist, vid) with a vid < 0 padding suffix, become one list of k_out
+ * entries ascending by (dist, vid + base[s]), padded with vid = -1.
+ *
+ * One wave per query and no sort. Every list is sorted already, so a real
+ * candidate's output rank is its position in its own list plus, for each
+ * other list, the number of entries whose key is smaller, and that number
+ * is a binary search. Keys order by distance (float `<`), then global id,
+ * then shard number; padding is greater than everything. Global ids of a
+ * well-formed shard set are distinct, so the shard number never decides
+ * there; it only keeps the ranks distinct, and every output slot written
+ * exactly once, when a caller's bases overlap. A candidate writes itself
+ * iff its rank is below k_out. Lanes stride over the S*k_in candidates.
+ *
+ * STAGED keeps the query's lists in LDS as (dist, global id) pairs;
+ * otherwise the searches read global memory. Same result either way.
+ * ------------------------------------------------------------------ */
+
+struct MergeKey { float dist; int32_t gvid; };   /* gvid < 0: padding */
+
+/* is list entry `e` of shard `es` ordered before the real candidate `c` of
+ * shard `cs`? */
+DEV bool merge_before(MergeKey e, int es, MergeKey c, int cs)
+{
+    if (e.gvid < 0) return false;
+    if (e.dist < c.dist) return true;
+    if (c.dist < e.dist) return false;
+    if (e.gvid != c.gvid) return e.gvid < c.gvid;
+    return es < cs;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(64)
+void merge_topk_kernel(const int32_t* __restrict__ vids,
+                       const float* __restrict__ dists, MergeBases bases,
+                       int S, int nq, int k_in, int k_out,
+                       int32_t* __restrict__ out_vids, float* __restrict__ out_dists)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char merge_lds[];
+    const int q = blockIdx.x;
+    if (q >= nq) return;
+    const int lane = threadIdx.x;
+    const int ncand = S * k_in;              /* <= 64 * MAX_K */
+    const size_t list_stride = (size_t)nq * k_in;
+    const int32_t* qv = vids + (size_t)q * k_in;    /* + s * list_stride */
+    const float* qd = dists + (size_t)q * k_in;
+    MergeKey* keys = (MergeKey*)merge_lds;   /* STAGED: [S][k_in] */
+
+    /* entry i of list s as a key */
+    auto entry = [&](int s, int i) -> MergeKey {
+        if constexpr (STAGED) return keys[s * k_in + i];
+        int32_t v = qv[s * list_stride + i];
+        return MergeKey{qd[s * list_stride + i], v < 0 ? -1 : v + bases.b[s]};
+    };
+
+    if constexpr (STAGED) {
+        for (int c = lane; c < ncand; c += 64) {
+            int s = c / k_in, i = c - s * k_in;
+            int32_t v = qv[s * list_stride + i];
+            keys[c] = MergeKey{qd[s * list_stride + i], v < 0 ? -1 : v + bases.b[s]};
+        }
+        __syncthreads();
+    }
+
+    int nreal = 0;                 /* wave-uniform: real candidates seen */
+    float paddist = MAXDIST;       /* wave-uniform: the inputs' own padding */
+    bool have_pad = false;
+    for (int c0 = 0; c0 < ncand; c0 += 64) {
+        const int c = c0 + lane;
+        const bool in = c < ncand;
+        int s = 0, i = 0;
+        MergeKey me{MAXDIST, -1};
+        if (in) {
+            s = c / k_in;
+            i = c - s * k_in;
+            me = entry(s, i);
+        }
+        const bool real = in && me.gvid >= 0;
+        const unsigned long long padmask = __ballot(in && !real);
+        nreal += __popcll(__ballot(real));
+        if (!have_pad && padmask) {
+            paddist = __shfl(me.dist, __ffsll((long long)padmask) - 1);
+            have_pad = true;
+        }
+        if (!real) continue;
+        int rank = i;
+        for (int t = 0; t < S && rank < k_out; t++) {
+            if (t == s) continue;
+            int lo = 0, hi = k_in;          /* first entry not before `me` */
+            while (lo < hi) {
+                int mid = (lo + hi) >> 1;
+                if (merge_before(entry(t, mid), t, me, s)) lo = mid + 1;
+                else hi = mid;
+            }
+            rank += lo;
+        }
+        if (rank < k_out) {
+            out_vids[(size_t)q * k_out + rank] = me.gvid;
+            out_dists[(size_t)q * k_out + rank] = me.dist;
+        }
+    }
+    for (int r = nreal + lane; r < k_out; r += 64) {
+        out_vids[(size_t)q * k_out + r] = -1;
+        out_dists[(size_t)q * k_out + r] = paddist;
+    }
+}
+
+int launch_merge_topk(const int32_t* vids, const float* dists,
+                      const MergeBases& bases, int nshards, int32_t nq,
+                      int32_t k_in, int32_t k_out, int32_t* out_vids,
+                      float* out_dists, void* stream)
+{
+    /* the kernel indexes nothing outside these bounds */
+    if (nshards < 1 || nshards > MAX_SHARDS || nq < 1 || k_in < 1 || k_in > MAX_K ||
+        k_out < 1 || k_out > MAX_K)
+        return (int)hipErrorInvalidValue;
+    const int ncand = nshards * k_in;
+    if (ncand <= MERGE_LDS_ENTRIES)
+        hipLaunchKernelGGL(merge_topk_kernel<true>, dim3(nq), dim3(64),
+                           (size_t)ncand * sizeof(MergeKey), (hipStream_t)stream,
+                           vids, dists, bases, nshards, nq, k_in, k_out, out_vids,
+                           out_dists);
+    else
+        hipLaunchKernelGGL(merge_topk_kernel<false>, dim3(nq), dim3(64), 0,
+                           (hipStream_t)stream, vids, dists, bases, nshards, nq,
+                           k_in, k_out, out_vids, out_dists);
+    return (int)hipGetLastError();
+}
+
+/* ------------------------------------------------------------------ *
  * launchers
  * ------------------------------------------------------------------ */
 
