@@ -42,12 +42,6 @@ struct SearchCfg {
                             LDS, the rest in the query's gheap_ng slab;
                             == ng_cap keeps the whole heap in LDS */
     int32_t vcap;                      /* visited table slots (pow2) */
-    int32_t spec_flags;  /* perf-only speculation (identical results):
-                            bit0 = warm neighbor vector lines during the
-                                   visited-CAS round;
-                            bit1 = next-pop lookahead (read next frontier
-                                   top's adjacency, read-only visited probe,
-                                   start unvisited vector loads) */
     int32_t prof;        /* 1 = per-phase cycle breakdown into stats
                             (stride PROF_STATS int32 per query; lane-0
                             clock64 marks — one wave per WG makes lane-0
@@ -56,7 +50,7 @@ struct SearchCfg {
 
 enum { PROF_STATS = 16 };  /* stats stride (int32) in prof mode; slots:
     0 checked, 1 popped, 2 seed, 3 pop, 4 row, 5 serial, 6 cas, 7 dist,
-    8 insert, 9 tree, 10 spec, 11 epilogue (cycles) */
+    8 insert, 9 tree, 10 epilogue (cycles), 11 NG-insert share of 8 */
 
 /* per-launch buffers */
 struct SearchBufs {
@@ -84,6 +78,10 @@ enum { SERIAL_STATE_BYTES = 64 };  /* LDS slot of the kernels' SerialState */
 #else
 #define SPTAG_HD
 #endif
+
+/* the reference's heap capacities (WorkSpace.h:265): frontier and tree heap */
+SPTAG_HD inline int32_t ref_ng_cap(int32_t max_check) { return max_check * 30; }
+SPTAG_HD inline int32_t ref_spt_cap(int32_t max_check) { return max_check * 10; }
 
 /* Dynamic-LDS carve-up of the one-wave-per-query kernels: byte offsets of
  * each region and the total. The kernels take their pointers and the
@@ -164,20 +162,18 @@ struct IterBufs {
 };
 
 int launch_bkt_iter(int valuetype, int distmethod, const DevIndex& di,
-                    const SearchCfg& cfg, const IterBufs& bufs, int batch,
-                    void* stream);
+                    const SearchCfg& cfg, const IterBufs& bufs, int batch);
 
 /* launchers implemented in kernels.hip; return hipError_t as int */
 int launch_bkt_search(int valuetype, int distmethod, bool heaps_in_lds,
                       const DevIndex& di, const SearchCfg& cfg,
-                      const SearchBufs& bufs, void* stream);
-int launch_gather_rows(void* dst, const void* src, int row_bytes,
-                       const int32_t* d_idx, int nrows, void* stream);
-int launch_scatter_rows(void* dst, const void* src, int row_bytes,
-                        const int32_t* d_idx, int nrows, void* stream);
+                      const SearchBufs& bufs);
+/* gather: dst row r = src row d_idx[r]; scatter: dst row d_idx[r] = src row r */
+int launch_copy_rows(bool gather, void* dst, const void* src, int row_bytes,
+                     const int32_t* d_idx, int nrows);
 int launch_truth(int valuetype, int distmethod, const DevIndex& di,
                  const void* queries, int32_t nq, int32_t k,
-                 int32_t* out_vids, float* out_dists, void* stream);
+                 int32_t* out_vids, float* out_dists);
 
 /* shard merge: at most MAX_SHARDS lists per query; the lists of one query
  * are staged in LDS up to MERGE_LDS_ENTRIES entries of 8 bytes (32 KiB) */
@@ -192,6 +188,6 @@ struct MergeBases { int32_t b[MAX_SHARDS]; };
 int launch_merge_topk(const int32_t* vids, const float* dists,
                       const MergeBases& bases, int nshards, int32_t nq,
                       int32_t k_in, int32_t k_out, int32_t* out_vids,
-                      float* out_dists, void* stream);
+                      float* out_dists);
 
 }  /* namespace sptag_amd */

@@ -31,7 +31,7 @@
 #include <thread>
 #include <vector>
 
-#include "common.h"
+#include "plan.h"
 
 using namespace sptag_amd;
 
@@ -123,6 +123,10 @@ struct HostIndex {
     long long last_checked = 0, last_popped = 0;
 
     size_t esz() const { return vt == VT_FLOAT ? 4 : 1; }
+    IndexParams params() const
+    {
+        return {algo, dim, esz(), init_pivots, other_pivots, nobetter_threshold};
+    }
     DevIndex dev() const {
         DevIndex di;
         di.vectors = d_vectors.as();
@@ -236,11 +240,38 @@ int upload(HostIndex* ix)
     return rc;
 }
 
-uint32_t next_pow2(uint32_t x)
+/* device vids and dists of a top-k result, n entries each (grow-only) */
+struct TopkOut {
+    DevBuf v, d;
+    int32_t* vids() const { return v.as<int32_t>(); }
+    float* dists() const { return d.as<float>(); }
+    int ensure(size_t n)
+    {
+        HIP_OR_FAIL(v.ensure(n * 4), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d.ensure(n * 4), SPTAG_AMD_ERR_OOM);
+        return SPTAG_AMD_OK;
+    }
+    int download(int32_t* out_vids, float* out_dists, size_t n) const
+    {
+        HIP_OR_FAIL(hipMemcpy(out_vids, v.as(), n * 4, hipMemcpyDeviceToHost),
+                    SPTAG_AMD_ERR_NOGPU);
+        HIP_OR_FAIL(hipMemcpy(out_dists, d.as(), n * 4, hipMemcpyDeviceToHost),
+                    SPTAG_AMD_ERR_NOGPU);
+        return SPTAG_AMD_OK;
+    }
+};
+
+/* Every environment variable the search path reads. Read once per search
+ * and never cached: callers change the environment between searches. */
+SearchKnobs read_knobs()
 {
-    uint32_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
+    SearchKnobs k;
+    if (const char* e = getenv("SPTAG_AMD_NG_CAP"))
+        k.ng_cap_override = std::max(1, atoi(e));   /* "0" is an override too */
+    if (const char* e = getenv("SPTAG_AMD_NG_GLEVELS")) k.ng_glevels = atoi(e);
+    k.prof = getenv("SPTAG_AMD_PROF") != nullptr;
+    k.debug = getenv("SPTAG_AMD_DEBUG") != nullptr;
+    return k;
 }
 
 /* read cursor over a file's bytes: take() refuses to run past the end */
@@ -465,35 +496,6 @@ void sptag_amd_free_index(SptagAmdIndex* ix)
     if (ix) delete ix;   /* the owners on the handle release the device side */
 }
 
-/* SearchCfg fields that the one-shot search and the iterator share: pivots,
- * threshold, dispatch flags, DistPriorityQueue size and the speculation
- * knob. `refine` selects the RefineSearchIndex dispatch (search_dup=0,
- * search_deleted=1) of the add path; the SearchIndex(QueryResult&,bool)
- * defaults otherwise. Heap and visited capacities are the caller's. */
-static SearchCfg base_cfg(const SptagAmdIndex* ix, int32_t nq, int32_t k,
-                          int32_t max_check, bool refine)
-{
-    SearchCfg cfg;
-    cfg.nq = nq;
-    cfg.k = k;
-    cfg.max_check = max_check;
-    cfg.init_pivots = ix->init_pivots;
-    cfg.other_pivots = ix->other_pivots;
-    cfg.nobetter_threshold = ix->nobetter_threshold;
-    cfg.search_dup = refine ? 0 : 1;
-    cfg.search_deleted = refine ? 1 : 0;
-    cfg.dpq_cap = std::max(max_check / 16, k);   /* WorkSpace.h:268 */
-    cfg.vcap = cfg.ng_cap = cfg.spt_cap = cfg.ng_lsplit = 0;
-    /* measured on MI355X (profiles/round2_experiments/ab_v5.txt): both
-     * speculation forms LOSE throughput at 10M/mc2048 (745k QPS off vs 622k
-     * on) — the extra touch loads consume request bandwidth the resident
-     * waves already saturate. Off by default; kept for experiments. */
-    cfg.spec_flags = 0;
-    if (const char* e = getenv("SPTAG_AMD_SPEC")) cfg.spec_flags = atoi(e);
-    cfg.prof = 0;
-    return cfg;
-}
-
 /* host copies of one pass's per-query stats and overflow flags */
 struct PassOut {
     int sstride;
@@ -516,8 +518,7 @@ static int run_pass(SptagAmdIndex* ix, bool heaps_in_lds, const SearchCfg& cfg,
     HIP_OR_FAIL(hipMemsetAsync(bufs.visited, 0, (size_t)nq * cfg.vcap * 4),
                 SPTAG_AMD_ERR_NOGPU);
     (void)hipEventRecord(ix->ev.start);
-    int err = launch_bkt_search(ix->vt, ix->dm, heaps_in_lds, ix->dev(), cfg, bufs,
-                                nullptr);
+    int err = launch_bkt_search(ix->vt, ix->dm, heaps_in_lds, ix->dev(), cfg, bufs);
     if (err != 0) {
         fprintf(stderr, "sptag_amd: %slaunch failed %d\n",
                 heaps_in_lds ? "" : "global-variant ", err);
@@ -525,8 +526,8 @@ static int run_pass(SptagAmdIndex* ix, bool heaps_in_lds, const SearchCfg& cfg,
     }
     (void)hipEventRecord(ix->ev.stop);
     if (d_idx) {
-        launch_scatter_rows(d_vids, bufs.out_vids, cfg.k * 4, d_idx, nq, nullptr);
-        launch_scatter_rows(d_dists, bufs.out_dists, cfg.k * 4, d_idx, nq, nullptr);
+        launch_copy_rows(false, d_vids, bufs.out_vids, cfg.k * 4, d_idx, nq);
+        launch_copy_rows(false, d_dists, bufs.out_dists, cfg.k * 4, d_idx, nq);
     }
     HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
     float ms = 0;
@@ -547,23 +548,23 @@ static int run_pass(SptagAmdIndex* ix, bool heaps_in_lds, const SearchCfg& cfg,
 /* SPTAG_AMD_PROF: per-phase cycle sums of one LDS pass (BKT kernels only) */
 static void prof_dump(const PassOut& out, int32_t nq, double ms)
 {
-    static const char* pname[10] = {
-        "seed", "pop", "row", "serial", "cas",
-        "dist", "insert", "tree", "spec", "sort"};
-    double tot[10] = {};
+    enum { NPHASE = 9 };
+    static const char* pname[NPHASE] = {
+        "seed", "pop", "row", "serial", "cas", "dist", "insert", "tree", "sort"};
+    double tot[NPHASE] = {};
     for (int32_t i = 0; i < nq; i++)
-        for (int p = 0; p < 10; p++)
+        for (int p = 0; p < NPHASE; p++)
             tot[p] += (double)out.stats[(size_t)out.sstride * i + 2 + p];
     double all = 0;
-    for (int p = 0; p < 10; p++) all += tot[p];
+    for (int p = 0; p < NPHASE; p++) all += tot[p];
     fprintf(stderr, "sptag_amd PROF (sum of per-query wave cycles, "
                     "%d queries, kernel %.2f ms):\n", nq, ms);
-    for (int p = 0; p < 10; p++)
+    for (int p = 0; p < NPHASE; p++)
         fprintf(stderr, "  %-7s %14.0f  (%5.1f%%)\n", pname[p], tot[p],
                 all > 0 ? 100.0 * tot[p] / all : 0.0);
     double ngi = 0;
     for (int32_t i = 0; i < nq; i++)
-        ngi += (double)out.stats[(size_t)out.sstride * i + 12];
+        ngi += (double)out.stats[(size_t)out.sstride * i + 2 + NPHASE];
     fprintf(stderr, "  (insert = ng-heap %14.0f + results-set rest)\n", ngi);
 }
 
@@ -574,68 +575,24 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
 {
     if (max_check <= 0) max_check = ix->default_maxcheck;
 
-    SearchCfg cfg = base_cfg(ix, nq, k, max_check, refine);
-    /* k-deep (refine-class) searches keep expanding far past MaxCheck —
-     * the budget is only consulted when a pop misses the k-deep results
-     * queue (BKTIndex.cpp:326) — so the visited table must scale with k
-     * as well (the reference's OptHashPosVector grows on demand,
-     * WorkSpace.h:119; a fixed GPU table errors loudly on saturation). */
-    cfg.vcap = (int32_t)next_pow2(
-        (uint32_t)std::max(4096, max_check * 4 + 64 * k));
-    /* LDS-variant capacities: sized to the TYPICAL traversal occupancy so
-     * several workgroups fit per CU; the rare query that outgrows them is
-     * rerun on the global-heap variant at the reference's own capacities
-     * (WorkSpace.h:265) — a speed tradeoff, never a semantic one. */
-    /* KDT inserts every computed neighbor into the frontier (no results-
-     * queue gate), so its occupancy tracks `checked` itself. */
-    cfg.ng_cap = ix->algo == ALGO_KDT ? max_check + 2048 : max_check / 2 + 512;
-    if (k > 64) cfg.ng_cap += 4 * k;   /* k-deep frontiers run larger */
-    if (const char* e = getenv("SPTAG_AMD_NG_CAP"))   /* perf experiments */
-        cfg.ng_cap = std::max(256, atoi(e));
-    cfg.spt_cap = 4096;
-    /* The reduced heaps emulate the reference's only while they are the
-     * smaller ones: a heap that is full at the reference's capacity
-     * (WorkSpace.h:265: 30*MaxCheck and 10*MaxCheck) replaces its largest
-     * last-level entry, one with room left just appends. Below MaxCheck 18
-     * (frontier) and 410 (tree heap) the sizes above are the larger ones,
-     * so they are cut to the reference's. */
-    cfg.ng_cap = std::min(cfg.ng_cap, max_check * 30);
-    cfg.spt_cap = std::min(cfg.spt_cap, max_check * 10);
-    /* Only the top levels of the frontier heap stay in LDS; the deepest
-     * NG_GLEVELS levels of a heap filled to ng_cap live in a per-query
-     * global slab. The headroom above the typical occupancy (~0.25 x
-     * MaxCheck) is what keeps the rerun rare, and it is mostly empty: in
-     * LDS it bought nothing but a lower count of resident queries per CU.
-     * Storage placement only — capacity and overflow are unchanged. */
-    int glevels = NG_GLEVELS;
-    if (const char* e = getenv("SPTAG_AMD_NG_GLEVELS"))   /* perf experiments */
-        glevels = std::min(3, std::max(0, atoi(e)));
-    cfg.ng_lsplit = ng_lds_split(cfg.ng_cap, glevels);
-    /* phase-cycle diagnostic (BKT kernels only — the KDT kernel writes
-     * plain stride-2 stats) */
-    cfg.prof = (getenv("SPTAG_AMD_PROF") && ix->algo == ALGO_BKT) ? 1 : 0;
-    const int sstride = cfg.prof ? PROF_STATS : 2;
-
-    /* The LDS pass runs only while its footprint stays within 64 KiB (and
-     * the device's own per-block limit): beyond that too few queries are
-     * resident per CU for it to pay, and the bound does not depend on what
-     * the device reports. */
-    int lds_limit = 64 * 1024;
+    /* 1. plan: every capacity of both passes */
+    const SearchKnobs knobs = read_knobs();
+    int lds_limit = LDS_PASS_MAX_BYTES;
     (void)hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock,
                                 ix->device);
-    lds_limit = std::min(lds_limit, 64 * 1024);
-    bool lds_ok = lds_bytes(ix->dim, ix->esz(), cfg, true) <= (size_t)lds_limit;
-    const bool ng_tail = lds_ok && cfg.ng_lsplit < cfg.ng_cap;
+    const SearchPlan plan =
+        plan_search(ix->params(), k, max_check, refine, lds_limit, knobs);
+    SearchCfg cfg = plan.lds;
+    cfg.nq = nq;
 
-    HIP_OR_FAIL(ix->d_visited.ensure((size_t)nq * cfg.vcap * 4), SPTAG_AMD_ERR_OOM);
+    /* 2. scratch of the LDS pass; visited, flags and stats serve both passes */
+    HIP_OR_FAIL(ix->d_visited.ensure(nq * plan.visited_bytes), SPTAG_AMD_ERR_OOM);
     HIP_OR_FAIL(ix->d_oflow.ensure((size_t)nq * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(ix->d_stats.ensure((size_t)nq * sstride * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(ix->d_stats.ensure((size_t)nq * plan.sstride * 4), SPTAG_AMD_ERR_OOM);
     ix->ev.ensure();
-    HIP_OR_FAIL(ix->d_gspt0.ensure((size_t)nq * ((size_t)cfg.spt_cap + 1) * 8),
-                SPTAG_AMD_ERR_OOM);
-    if (ng_tail)
-        HIP_OR_FAIL(ix->d_gng0.ensure((size_t)nq * ((size_t)cfg.ng_cap + 1) * 8),
-                    SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(ix->d_gspt0.ensure(nq * plan.gspt0_bytes), SPTAG_AMD_ERR_OOM);
+    if (plan.ng_tail)
+        HIP_OR_FAIL(ix->d_gng0.ensure(nq * plan.gng0_bytes), SPTAG_AMD_ERR_OOM);
 
     SearchBufs bufs;
     bufs.queries = d_q;
@@ -644,22 +601,23 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
     bufs.visited = ix->d_visited.as<int32_t>();
     bufs.oflow = ix->d_oflow.as<int32_t>();
     bufs.stats = ix->d_stats.as<int32_t>();
-    bufs.gheap_ng = ng_tail ? ix->d_gng0.as() : nullptr;
+    bufs.gheap_ng = plan.ng_tail ? ix->d_gng0.as() : nullptr;
     bufs.gheap_spt = ix->d_gspt0.as();
 
+    /* 3. LDS pass, 4. pick the reruns */
     ix->last_kernel_ms = 0;
     ix->last_checked = 0;
     ix->last_popped = 0;
-    PassOut out(sstride, nq);
+    PassOut out(plan.sstride, nq);
     std::vector<int32_t> redo;
-    bool all_global = !lds_ok;
-    if (lds_ok) {
+    bool all_global = !plan.lds_ok;
+    if (plan.lds_ok) {
         int rc = run_pass(ix, true, cfg, bufs, out);
         if (rc != SPTAG_AMD_OK) return rc;
         for (int32_t i = 0; i < nq; i++)
             if (out.oflow[i]) redo.push_back(i);
         if (cfg.prof) prof_dump(out, nq, ix->last_kernel_ms);
-        if (!redo.empty() && getenv("SPTAG_AMD_DEBUG"))
+        if (!redo.empty() && knobs.debug)
             fprintf(stderr, "sptag_amd: %zu/%d queries overflowed (rerun)\n",
                     redo.size(), nq);
         if (redo.size() * 2 > (size_t)nq) {
@@ -670,18 +628,17 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
         }
     }
 
+    /* 5. global-heap pass at the reference's capacities */
     int32_t gq_n = all_global ? nq : (int32_t)redo.size();
     if (gq_n == 0) return SPTAG_AMD_OK;
-    if (getenv("SPTAG_AMD_DEBUG"))
+    if (knobs.debug)
         fprintf(stderr, "sptag_amd: global-heap pass for %d/%d queries\n", gq_n, nq);
     SearchCfg c2 = cfg;
     c2.nq = gq_n;
-    c2.ng_cap = max_check * 30;     /* reference capacities */
-    c2.spt_cap = max_check * 10;
-    HIP_OR_FAIL(ix->d_gng.ensure((size_t)gq_n * ((size_t)c2.ng_cap + 1) * 8),
-                SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(ix->d_gspt.ensure((size_t)gq_n * ((size_t)c2.spt_cap + 1) * 8),
-                SPTAG_AMD_ERR_OOM);
+    c2.ng_cap = plan.g_ng_cap;
+    c2.spt_cap = plan.g_spt_cap;
+    HIP_OR_FAIL(ix->d_gng.ensure(gq_n * plan.gng_bytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(ix->d_gspt.ensure(gq_n * plan.gspt_bytes), SPTAG_AMD_ERR_OOM);
     SearchBufs b2 = bufs;
     b2.gheap_ng = ix->d_gng.as();
     b2.gheap_spt = ix->d_gspt.as();
@@ -697,7 +654,7 @@ static int search_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq,
         int32_t* d_v2 = (int32_t*)(d_q2 + qseg);
         HIP_OR_FAIL(hipMemcpy(d_idx, redo.data(), (size_t)gq_n * 4,
                               hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-        launch_gather_rows(d_q2, d_q, (int)row, d_idx, gq_n, nullptr);
+        launch_copy_rows(true, d_q2, d_q, (int)row, d_idx, gq_n);
         b2.queries = d_q2;
         b2.out_vids = d_v2;
         b2.out_dists = (float*)(d_v2 + (size_t)gq_n * k);
@@ -751,21 +708,14 @@ int sptag_amd_search_batch(SptagAmdIndex* ix, const void* queries, int32_t nq,
     std::lock_guard<std::mutex> g(ix->lock);
     HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
 
-    const size_t obytes = (size_t)nq * k * 4;
-    DevBuf d_q, d_vids, d_dists;
-    HIP_OR_FAIL(d_q.alloc((size_t)nq * ix->dim * ix->esz()), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(d_vids.alloc(obytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(d_dists.alloc(obytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(d_q.as(), queries, (size_t)nq * ix->dim * ix->esz(),
-                          hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-    rc = search_device_core(ix, d_q.as(), nq, k, max_check, d_vids.as<int32_t>(),
-                            d_dists.as<float>());
-    if (rc != SPTAG_AMD_OK) return rc;
-    HIP_OR_FAIL(hipMemcpy(out_vids, d_vids.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_dists, d_dists.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    return SPTAG_AMD_OK;
+    const size_t n = (size_t)nq * k;
+    DevBuf d_q;
+    TopkOut out;
+    if ((rc = dev_upload(d_q, queries, (size_t)nq * ix->dim * ix->esz())) != SPTAG_AMD_OK)
+        return rc;
+    if ((rc = out.ensure(n)) != SPTAG_AMD_OK) return rc;
+    rc = search_device_core(ix, d_q.as(), nq, k, max_check, out.vids(), out.dists());
+    return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, n);
 }
 
 void sptag_amd_last_stats(SptagAmdIndex* ix, double* kernel_ms,
@@ -779,11 +729,13 @@ void sptag_amd_last_stats(SptagAmdIndex* ix, double* kernel_ms,
 
 struct SptagAmdIterBatch {
     SptagAmdIndex* ix = nullptr;
-    int32_t nq = 0, max_check = 0, vcap = 0, ng_cap = 0, spt_cap = 0, dpq_alloc = 0;
+    int32_t nq = 0, max_check = 0;
+    IterPlan plan = {};
     /* queries and persistent traversal state */
     DevBuf d_q, d_ng, d_spt, d_dpq, d_visited, d_state;
-    /* per-call outputs; d_ov/d_od grow with the largest batch asked for */
-    DevBuf d_ov, d_od, d_oc, d_or;
+    /* per-call outputs; `out` grows with the largest batch asked for */
+    TopkOut out;
+    DevBuf d_oc, d_or;
 };
 
 SptagAmdIterBatch* sptag_amd_iter_create(SptagAmdIndex* ix, const void* queries,
@@ -806,18 +758,15 @@ SptagAmdIterBatch* sptag_amd_iter_create(SptagAmdIndex* ix, const void* queries,
     it->ix = ix;
     it->nq = nq;
     it->max_check = max_check;
-    it->ng_cap = max_check * 30;    /* reference WorkSpace.h:265 capacities */
-    it->spt_cap = max_check * 10;
-    it->dpq_alloc = std::max(max_check / 16, (int)MAX_K);
-    it->vcap = (int32_t)next_pow2((uint32_t)std::max(4096, max_check * 4));
+    const IterPlan& p = it->plan = plan_iter(max_check);
     std::vector<IterState> init(nq);
     for (auto& st : init) { st = IterState{}; st.first = 1; }
-    const size_t vbytes = (size_t)nq * it->vcap * 4;
+    const size_t vbytes = (size_t)nq * p.vcap * 4;
     if (dev_upload(it->d_q, queries, (size_t)nq * ix->dim * ix->esz()) != SPTAG_AMD_OK)
         return nullptr;
-    HIP_OR_FAIL(it->d_ng.alloc((size_t)nq * (it->ng_cap + 1) * 8), nullptr);
-    HIP_OR_FAIL(it->d_spt.alloc((size_t)nq * (it->spt_cap + 1) * 8), nullptr);
-    HIP_OR_FAIL(it->d_dpq.alloc((size_t)nq * (it->dpq_alloc + 1) * 4), nullptr);
+    HIP_OR_FAIL(it->d_ng.alloc(nq * heap_slab_bytes(p.ng_cap)), nullptr);
+    HIP_OR_FAIL(it->d_spt.alloc(nq * heap_slab_bytes(p.spt_cap)), nullptr);
+    HIP_OR_FAIL(it->d_dpq.alloc((size_t)nq * (p.dpq_alloc + 1) * 4), nullptr);
     HIP_OR_FAIL(it->d_visited.alloc(vbytes), nullptr);
     HIP_OR_FAIL(hipMemset(it->d_visited.as(), 0, vbytes), nullptr);
     HIP_OR_FAIL(it->d_oc.alloc((size_t)nq * 4), nullptr);
@@ -841,14 +790,15 @@ int sptag_amd_iter_next(SptagAmdIterBatch* it, int32_t batch,
     SptagAmdIndex* ix = it->ix;
     std::lock_guard<std::mutex> g(ix->lock);
     HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
-    const size_t obytes = (size_t)it->nq * batch * 4;
-    HIP_OR_FAIL(it->d_ov.ensure(obytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(it->d_od.ensure(obytes), SPTAG_AMD_ERR_OOM);
+    const size_t n = (size_t)it->nq * batch;
+    int rc = it->out.ensure(n);
+    if (rc != SPTAG_AMD_OK) return rc;
     /* dpq_cap comes out as the ResetResult cap, max(max_check/16, batch) */
-    SearchCfg cfg = base_cfg(ix, it->nq, batch, it->max_check, false);
-    cfg.vcap = it->vcap;
-    cfg.ng_cap = it->ng_cap;
-    cfg.spt_cap = it->spt_cap;
+    SearchCfg cfg = base_cfg(ix->params(), batch, it->max_check, false);
+    cfg.nq = it->nq;
+    cfg.vcap = it->plan.vcap;
+    cfg.ng_cap = it->plan.ng_cap;
+    cfg.spt_cap = it->plan.spt_cap;
 
     IterBufs ib;
     ib.queries = it->d_q.as();
@@ -857,11 +807,11 @@ int sptag_amd_iter_next(SptagAmdIterBatch* it, int32_t batch,
     ib.dpq = it->d_dpq.as<float>();
     ib.visited = it->d_visited.as<int32_t>();
     ib.state = it->d_state.as<IterState>();
-    ib.out_vids = it->d_ov.as<int32_t>();
-    ib.out_dists = it->d_od.as<float>();
+    ib.out_vids = it->out.vids();
+    ib.out_dists = it->out.dists();
     ib.out_counts = it->d_oc.as<int32_t>();
     ib.out_relaxed = it->d_or.as<int32_t>();
-    int err = launch_bkt_iter(ix->vt, ix->dm, ix->dev(), cfg, ib, batch, nullptr);
+    int err = launch_bkt_iter(ix->vt, ix->dm, ix->dev(), cfg, ib, batch);
     if (err != 0) {
         fprintf(stderr, "sptag_amd: iter launch failed %d\n", err);
         return SPTAG_AMD_ERR_INTERNAL;
@@ -881,14 +831,11 @@ int sptag_amd_iter_next(SptagAmdIterBatch* it, int32_t batch,
             fprintf(stderr,
                     "sptag_amd: iterator query %d overflowed at reference "
                     "capacities (visited-table saturation, %d slots); "
-                    "create the iterator with a larger MaxCheck\n", i, it->vcap);
+                    "create the iterator with a larger MaxCheck\n", i, it->plan.vcap);
             return SPTAG_AMD_ERR_INTERNAL;
         }
     }
-    HIP_OR_FAIL(hipMemcpy(out_vids, ib.out_vids, obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_dists, ib.out_dists, obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
+    if ((rc = it->out.download(out_vids, out_dists, n)) != SPTAG_AMD_OK) return rc;
     HIP_OR_FAIL(hipMemcpy(out_counts, ib.out_counts, (size_t)it->nq * 4,
                           hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
     if (out_relaxed)
@@ -905,22 +852,17 @@ int sptag_amd_truth(SptagAmdIndex* ix, const void* queries, int32_t nq,
     std::lock_guard<std::mutex> g(ix->lock);
     HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
 
-    const size_t qbytes = (size_t)nq * ix->dim * ix->esz(), obytes = (size_t)nq * k * 4;
-    DevBuf d_q, d_v, d_d;
-    HIP_OR_FAIL(d_q.alloc(qbytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(d_v.alloc(obytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(d_d.alloc(obytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(hipMemcpy(d_q.as(), queries, qbytes, hipMemcpyHostToDevice),
-                SPTAG_AMD_ERR_NOGPU);
-    if (launch_truth(ix->vt, ix->dm, ix->dev(), d_q.as(), nq, k, d_v.as<int32_t>(),
-                     d_d.as<float>(), nullptr) != 0)
+    const size_t n = (size_t)nq * k;
+    DevBuf d_q;
+    TopkOut out;
+    int rc = dev_upload(d_q, queries, (size_t)nq * ix->dim * ix->esz());
+    if (rc != SPTAG_AMD_OK) return rc;
+    if ((rc = out.ensure(n)) != SPTAG_AMD_OK) return rc;
+    if (launch_truth(ix->vt, ix->dm, ix->dev(), d_q.as(), nq, k, out.vids(),
+                     out.dists()) != 0)
         return SPTAG_AMD_ERR_NOGPU;
     HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_vids, d_v.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_dists, d_d.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    return SPTAG_AMD_OK;
+    return out.download(out_vids, out_dists, n);
 }
 
 /* Host-side distance restatements for the add path's edge arithmetic
@@ -1099,9 +1041,9 @@ int sptag_amd_add(SptagAmdIndex* ix, const void* vectors, int32_t nadd,
     /* d_rows/d_rowidx stage the batched changed-row upload: one H2D + one
      * scatter per added node instead of one 128 B hipMemcpy per touched
      * edge (the round-1 form did up to ~500 tiny copies per add). */
-    DevBuf d_v, d_d, d_q, d_rows, d_rowidx;
-    HIP_OR_FAIL(d_v.alloc((size_t)k * 4), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(d_d.alloc((size_t)k * 4), SPTAG_AMD_ERR_OOM);
+    TopkOut out;
+    DevBuf d_q, d_rows, d_rowidx;
+    if ((rc = out.ensure(k)) != SPTAG_AMD_OK) return rc;
     HIP_OR_FAIL(d_q.alloc((size_t)ix->dim * esz), SPTAG_AMD_ERR_OOM);
     HIP_OR_FAIL(d_rows.alloc((size_t)(k + 1) * ix->deg * 4), SPTAG_AMD_ERR_OOM);
     HIP_OR_FAIL(d_rowidx.alloc((size_t)(k + 1) * 4), SPTAG_AMD_ERR_OOM);
@@ -1111,12 +1053,9 @@ int sptag_amd_add(SptagAmdIndex* ix, const void* vectors, int32_t nadd,
         HIP_OR_FAIL(hipMemcpy(d_q.as(), hvec(ix, node), (size_t)ix->dim * esz,
                               hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
         rc = search_device_core(ix, d_q.as(), 1, k, 8192 /*MaxCheckForRefineGraph*/,
-                                d_v.as<int32_t>(), d_d.as<float>(), true);
+                                out.vids(), out.dists(), true);
         if (rc != SPTAG_AMD_OK) return rc;
-        HIP_OR_FAIL(hipMemcpy(rv.data(), d_v.as(), (size_t)k * 4,
-                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
-        HIP_OR_FAIL(hipMemcpy(rd.data(), d_d.as(), (size_t)k * 4,
-                              hipMemcpyDeviceToHost), SPTAG_AMD_ERR_NOGPU);
+        if ((rc = out.download(rv.data(), rd.data(), k)) != SPTAG_AMD_OK) return rc;
         host_rebuild_neighbors(ix, node, rv.data(), rd.data(), k);
         int nrows = 0;
         hidx[nrows++] = node;
@@ -1138,8 +1077,8 @@ int sptag_amd_add(SptagAmdIndex* ix, const void* vectors, int32_t nadd,
                               hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
         HIP_OR_FAIL(hipMemcpy(d_rowidx.as(), hidx.data(), (size_t)nrows * 4,
                               hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
-        launch_scatter_rows(ix->d_graph.as(), d_rows.as(), ix->deg * 4,
-                            d_rowidx.as<int32_t>(), nrows, nullptr);
+        launch_copy_rows(false, ix->d_graph.as(), d_rows.as(), ix->deg * 4,
+                         d_rowidx.as<int32_t>(), nrows);
         HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
     }
     return SPTAG_AMD_OK;
@@ -1389,7 +1328,7 @@ static int merge_on_device(const MergeBases& bases, int32_t nshards, int32_t nq,
                            const float* d_dists, int32_t* d_out_vids, float* d_out_dists)
 {
     int err = launch_merge_topk(d_vids, d_dists, bases, nshards, nq, k_in, k_out,
-                                d_out_vids, d_out_dists, nullptr);
+                                d_out_vids, d_out_dists);
     if (err != 0) {
         fprintf(stderr, "sptag_amd: merge launch failed %d\n", err);
         return SPTAG_AMD_ERR_INTERNAL;
@@ -1474,21 +1413,16 @@ int sptag_amd_merge_topk(int device, int32_t nshards, int32_t nq, int32_t k_in,
                            out_dists);
     if (rc != SPTAG_AMD_OK) return rc;
     HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
-    const size_t ibytes = (size_t)nshards * nq * k_in * 4, obytes = (size_t)nq * k_out * 4;
-    DevBuf d_v, d_d, d_ov, d_od;
+    const size_t ibytes = (size_t)nshards * nq * k_in * 4, n = (size_t)nq * k_out;
+    DevBuf d_v, d_d;
+    TopkOut out;
     if ((rc = dev_upload(d_v, vids, ibytes)) != SPTAG_AMD_OK) return rc;
     if ((rc = dev_upload(d_d, dists, ibytes)) != SPTAG_AMD_OK) return rc;
-    HIP_OR_FAIL(d_ov.alloc(obytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(d_od.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    if ((rc = out.ensure(n)) != SPTAG_AMD_OK) return rc;
     rc = sptag_amd_merge_topk_device(device, nshards, nq, k_in, k_out,
                                      d_v.as<int32_t>(), d_d.as<float>(), vid_base,
-                                     d_ov.as<int32_t>(), d_od.as<float>());
-    if (rc != SPTAG_AMD_OK) return rc;
-    HIP_OR_FAIL(hipMemcpy(out_vids, d_ov.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_dists, d_od.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    return SPTAG_AMD_OK;
+                                     out.vids(), out.dists());
+    return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, n);
 }
 
 SptagAmdShards* sptag_amd_shards_create(SptagAmdIndex* const* shards, int32_t nshards,
@@ -1578,19 +1512,14 @@ int sptag_amd_shards_search_batch(SptagAmdShards* set, const void* queries, int3
     if (!out_vids || !out_dists) return SPTAG_AMD_ERR_PARAM;
     HIP_OR_FAIL(hipSetDevice(set->groups[0].device), SPTAG_AMD_ERR_NOGPU);
     const SptagAmdIndex* ix0 = set->shards[0];
-    const size_t qbytes = (size_t)nq * ix0->dim * ix0->esz(), obytes = (size_t)nq * k * 4;
-    DevBuf d_q, d_v, d_d;
+    const size_t qbytes = (size_t)nq * ix0->dim * ix0->esz(), n = (size_t)nq * k;
+    DevBuf d_q;
+    TopkOut out;
     if ((rc = dev_upload(d_q, queries, qbytes)) != SPTAG_AMD_OK) return rc;
-    HIP_OR_FAIL(d_v.alloc(obytes), SPTAG_AMD_ERR_OOM);
-    HIP_OR_FAIL(d_d.alloc(obytes), SPTAG_AMD_ERR_OOM);
+    if ((rc = out.ensure(n)) != SPTAG_AMD_OK) return rc;
     rc = sptag_amd_shards_search_batch_device(set, d_q.as(), nq, k, max_check,
-                                              d_v.as<int32_t>(), d_d.as<float>());
-    if (rc != SPTAG_AMD_OK) return rc;
-    HIP_OR_FAIL(hipMemcpy(out_vids, d_v.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    HIP_OR_FAIL(hipMemcpy(out_dists, d_d.as(), obytes, hipMemcpyDeviceToHost),
-                SPTAG_AMD_ERR_NOGPU);
-    return SPTAG_AMD_OK;
+                                              out.vids(), out.dists());
+    return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, n);
 }
 
 int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries, int32_t nq,

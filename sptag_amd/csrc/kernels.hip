@@ -594,13 +594,13 @@ DEV void search_heaps(const SearchCfg& cfg, const SearchBufs& bufs, const LdsLay
                       int q, HeapRef& ng, HeapRef& spt)
 {
     extern __shared__ char smem[];
-    ng.cap = cfg.ng_cap;  ng.ref_cap = cfg.max_check * 30;   /* WorkSpace.h:265 */
+    ng.cap = cfg.ng_cap;  ng.ref_cap = ref_ng_cap(cfg.max_check);
     ng.lds = LDSHEAP ? (NodeDist*)(smem + L.ng) : nullptr;
     ng.lsplit = LDSHEAP ? cfg.ng_lsplit : 0;
     /* with ng_lsplit == ng_cap no index reaches `a` and the host passes no slab */
     ng.a = bufs.gheap_ng ? (NodeDist*)bufs.gheap_ng + (size_t)q * (cfg.ng_cap + 1)
                          : nullptr;
-    spt.cap = cfg.spt_cap; spt.ref_cap = cfg.max_check * 10;
+    spt.cap = cfg.spt_cap; spt.ref_cap = ref_spt_cap(cfg.max_check);
     spt.a = (NodeDist*)bufs.gheap_spt + (size_t)q * (cfg.spt_cap + 1);
     spt.lds = (NodeDist*)(smem + L.spt_tier);
     spt.lsplit = SPT_LDS_TIER;
@@ -822,53 +822,20 @@ DEV Row load_row(QCtx<T>& c, int32_t node)
 
 /* neighbor expansion (BKTIndex.cpp:333-345): compact the unvisited
  * neighbors of `r` (row order preserved) into istage[0..ncand) and return
- * ncand; ends in a barrier.
- * spec bit0: while the visited-CAS round is in flight, warm every
- * neighbor's vector lines (one byte per 128B line) — the unvisited
- * ones are exactly what stage_dists reads next, so the two
- * dependent HBM round trips (CAS, vector gather) overlap; the
- * re-visited rows were read recently and mostly hit L2/L3. */
+ * ncand; ends in a barrier. */
 template <typename T>
 DEV int expand_neighbors(QCtx<T>& c, const Row& r)
 {
     int already = 1;
-    uint32_t tsink = 0;
-    if (c.lane < r.firstneg) {
-        if (c.cfg->spec_flags & 1) tsink = touch_lines<T>(*c.di, r.nn);
+    if (c.lane < r.firstneg)
         already = visited_test_insert(c.vtab, c.vmask, r.nn, &c.ss->oflow);
-    }
     uint64_t candm = __ballot(c.lane < r.firstneg && !already);
-    asm volatile("" :: "v"(tsink));
     if ((candm >> c.lane) & 1) {
         int pos = __popcll(candm & ((1ull << c.lane) - 1));
         c.istage[pos] = r.nn;
     }
     __syncthreads();
     return __popcll(candm);
-}
-
-/* spec bit1: lookahead on the next pop (perf-only — the frontier
- * top rarely changes between here and the next iteration's pop).
- * Read its adjacency row, probe the visited table READ-ONLY (first
- * slot; stale/partial answers only cost an extra touch), and start
- * the unvisited neighbors' vector loads. The loads stay in flight
- * across the barrier — `sink` is consumed after the next pop. */
-template <typename T>
-DEV void lookahead_next(QCtx<T>& c, uint32_t& sink)
-{
-    if (!(c.cfg->spec_flags & 2)) return;
-    const int deg = c.di->deg;
-    if (c.lane == 0) c.ss->popped = ndheap_top(c.ng, c.ss->ng_count);
-    __syncthreads();
-    int32_t nxt = c.ss->popped.node;
-    if (nxt >= 0 && c.lane < deg) {
-        int32_t t = c.di->graph[(size_t)nxt * deg + c.lane];
-        if (t >= 0) {
-            uint32_t key = (uint32_t)(t + 1);
-            uint32_t h = (key * 2654435761u) & c.vmask;
-            if (c.vtab[h] != (int32_t)key) sink += touch_lines<T>(*c.di, t);
-        }
-    }
 }
 
 /* ------------------------------------------------------------------ *
@@ -884,7 +851,7 @@ DEV void lookahead_next(QCtx<T>& c, uint32_t& sink)
  * wave-accurate. */
 template <bool PROF>
 struct PhaseClock {
-    uint64_t pc[10] = {};
+    uint64_t pc[9] = {};
     uint64_t t = 0, ng = 0, t_ng = 0;
     DEV void mark() { if (PROF && threadIdx.x == 0) t = clock64(); }
     DEV void acc(int i)
@@ -901,9 +868,9 @@ struct PhaseClock {
     DEV void store(int32_t* s) const   /* stats slots 2..15 */
     {
 #pragma unroll
-        for (int i = 0; i < 10; i++) s[2 + i] = (int32_t)pc[i];
-        s[12] = (int32_t)ng;
-        s[13] = s[14] = s[15] = 0;
+        for (int i = 0; i < 9; i++) s[2 + i] = (int32_t)pc[i];
+        s[11] = (int32_t)ng;
+        s[12] = s[13] = s[14] = s[15] = 0;
     }
 };
 
@@ -939,7 +906,6 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     clk.acc(0);
 
     int popped = 0;
-    uint32_t spec_sink = 0;   /* keeps lookahead loads alive across barriers */
 
     for (;;) {
         __syncthreads();
@@ -948,7 +914,6 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         if (lane == 0) ss->popped = ndheap_pop(c.ng, &ss->ng_count);
         __syncthreads();
         clk.acc(1);
-        asm volatile("" :: "v"(spec_sink));   /* lookahead loads land here */
         popped++;
         NodeDist gnode = ss->popped;
         const Row row = load_row(c, gnode.node);
@@ -1024,15 +989,13 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         if (ss->want_tree)
             search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked);
         clk.acc(7);
-        lookahead_next(c, spec_sink);
-        clk.acc(8);
     }
     __syncthreads();
 
     if (lane == 0) bufs.oflow[q] = ss->oflow;
     clk.mark();
     write_topk(qrs, cfg.k, q, bufs.out_vids, bufs.out_dists);
-    clk.acc(9);
+    clk.acc(8);
     if (lane == 0 && bufs.stats) {
         int32_t* s = bufs.stats + (size_t)q * (PROF ? (int)PROF_STATS : 2);
         s[0] = ss->checked;
@@ -1264,14 +1227,12 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     kdt_search_trees_dev<T, DM, DC>(c, cfg.init_pivots);
 
     int popped = 0;
-    uint32_t spec_sink = 0;
 
     for (;;) {
         __syncthreads();
         if (ss->ng_count <= 0 || ss->terminate || ss->oflow) break;
         if (lane == 0) ss->popped = ndheap_pop(c.ng, &ss->ng_count);
         __syncthreads();
-        asm volatile("" :: "v"(spec_sink));
         popped++;
         NodeDist gnode = ss->popped;
         const Row row = load_row(c, gnode.node);
@@ -1317,7 +1278,6 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         if (ss->break_flag) break;
         if (ss->want_tree)
             kdt_search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked);
-        lookahead_next(c, spec_sink);
     }
     __syncthreads();
 
@@ -1393,26 +1353,13 @@ __global__ void copy_rows_kernel(char* dst, const char* src, int row_bytes,
     }
 }
 
-template <bool SRC_INDEXED>
-static int launch_copy_rows(void* dst, const void* src, int row_bytes,
-                            const int32_t* d_idx, int nrows, void* stream)
+int launch_copy_rows(bool gather, void* dst, const void* src, int row_bytes,
+                     const int32_t* d_idx, int nrows)
 {
-    hipLaunchKernelGGL(copy_rows_kernel<SRC_INDEXED>, dim3(nrows), dim3(64), 0,
-                       (hipStream_t)stream, (char*)dst, (const char*)src,
+    hipLaunchKernelGGL(gather ? copy_rows_kernel<true> : copy_rows_kernel<false>,
+                       dim3(nrows), dim3(64), 0, nullptr, (char*)dst, (const char*)src,
                        row_bytes, d_idx, nrows);
     return (int)hipGetLastError();
-}
-
-int launch_gather_rows(void* dst, const void* src, int row_bytes,
-                       const int32_t* d_idx, int nrows, void* stream)
-{
-    return launch_copy_rows<true>(dst, src, row_bytes, d_idx, nrows, stream);
-}
-
-int launch_scatter_rows(void* dst, const void* src, int row_bytes,
-                        const int32_t* d_idx, int nrows, void* stream)
-{
-    return launch_copy_rows<false>(dst, src, row_bytes, d_idx, nrows, stream);
 }
 
 /* ------------------------------------------------------------------ *
@@ -1528,22 +1475,18 @@ void merge_topk_kernel(const int32_t* __restrict__ vids,
 int launch_merge_topk(const int32_t* vids, const float* dists,
                       const MergeBases& bases, int nshards, int32_t nq,
                       int32_t k_in, int32_t k_out, int32_t* out_vids,
-                      float* out_dists, void* stream)
+                      float* out_dists)
 {
     /* the kernel indexes nothing outside these bounds */
     if (nshards < 1 || nshards > MAX_SHARDS || nq < 1 || k_in < 1 || k_in > MAX_K ||
         k_out < 1 || k_out > MAX_K)
         return (int)hipErrorInvalidValue;
     const int ncand = nshards * k_in;
-    if (ncand <= MERGE_LDS_ENTRIES)
-        hipLaunchKernelGGL(merge_topk_kernel<true>, dim3(nq), dim3(64),
-                           (size_t)ncand * sizeof(MergeKey), (hipStream_t)stream,
-                           vids, dists, bases, nshards, nq, k_in, k_out, out_vids,
-                           out_dists);
-    else
-        hipLaunchKernelGGL(merge_topk_kernel<false>, dim3(nq), dim3(64), 0,
-                           (hipStream_t)stream, vids, dists, bases, nshards, nq,
-                           k_in, k_out, out_vids, out_dists);
+    const bool staged = ncand <= MERGE_LDS_ENTRIES;
+    hipLaunchKernelGGL(staged ? merge_topk_kernel<true> : merge_topk_kernel<false>,
+                       dim3(nq), dim3(64), staged ? (size_t)ncand * sizeof(MergeKey) : 0,
+                       nullptr, vids, dists, bases, nshards, nq, k_in, k_out, out_vids,
+                       out_dists);
     return (int)hipGetLastError();
 }
 
@@ -1576,56 +1519,49 @@ static int dispatch_kernel(int vt, int dm, int dim, F&& f)
 
 template <typename T, int DM, int DC, bool LDSHEAP>
 static int launch_one(const DevIndex& di, const SearchCfg& cfg,
-                      const SearchBufs& bufs, hipStream_t stream)
+                      const SearchBufs& bufs)
 {
     size_t lds = lds_bytes(di.dim, sizeof(T), cfg, LDSHEAP);
-    dim3 grid(cfg.nq), block(64);
-    if (di.algo == ALGO_KDT)
-        hipLaunchKernelGGL((kdt_search_kernel<T, DM, DC, LDSHEAP>), grid, block, lds,
-                           stream, di, cfg, bufs);
-    else if (cfg.prof)
-        hipLaunchKernelGGL((bkt_search_kernel<T, DM, DC, LDSHEAP, true>), grid,
-                           block, lds, stream, di, cfg, bufs);
-    else
-        hipLaunchKernelGGL((bkt_search_kernel<T, DM, DC, LDSHEAP, false>), grid,
-                           block, lds, stream, di, cfg, bufs);
+    auto kernel = di.algo == ALGO_KDT ? kdt_search_kernel<T, DM, DC, LDSHEAP>
+                  : cfg.prof          ? bkt_search_kernel<T, DM, DC, LDSHEAP, true>
+                                      : bkt_search_kernel<T, DM, DC, LDSHEAP, false>;
+    hipLaunchKernelGGL(kernel, dim3(cfg.nq), dim3(64), lds, nullptr, di, cfg, bufs);
     return (int)hipGetLastError();
 }
 
 int launch_bkt_search(int vt, int dm, bool heaps_in_lds, const DevIndex& di,
-                      const SearchCfg& cfg, const SearchBufs& bufs, void* stream)
+                      const SearchCfg& cfg, const SearchBufs& bufs)
 {
     return dispatch_kernel(vt, dm, di.dim, [&](auto t, auto d, auto c) {
         using T = typename decltype(t)::type;
         constexpr int DM = decltype(d)::value, DC = decltype(c)::value;
-        hipStream_t s = (hipStream_t)stream;
-        return heaps_in_lds ? launch_one<T, DM, DC, true>(di, cfg, bufs, s)
-                            : launch_one<T, DM, DC, false>(di, cfg, bufs, s);
+        return heaps_in_lds ? launch_one<T, DM, DC, true>(di, cfg, bufs)
+                            : launch_one<T, DM, DC, false>(di, cfg, bufs);
     });
 }
 
 int launch_bkt_iter(int vt, int dm, const DevIndex& di, const SearchCfg& cfg,
-                    const IterBufs& ib, int batch, void* stream)
+                    const IterBufs& ib, int batch)
 {
     return dispatch_kernel(vt, dm, di.dim, [&](auto t, auto d, auto c) {
         using T = typename decltype(t)::type;
         constexpr int DM = decltype(d)::value, DC = decltype(c)::value;
         size_t lds = iter_lds_layout(di.dim, sizeof(T), batch).total;
         hipLaunchKernelGGL((bkt_iter_kernel<T, DM, DC>), dim3(cfg.nq),
-                           dim3(64), lds, (hipStream_t)stream, di, cfg, ib, batch);
+                           dim3(64), lds, nullptr, di, cfg, ib, batch);
         return (int)hipGetLastError();
     });
 }
 
 int launch_truth(int vt, int dm, const DevIndex& di, const void* queries,
-                 int32_t nq, int32_t k, int32_t* ov, float* od, void* stream)
+                 int32_t nq, int32_t k, int32_t* ov, float* od)
 {
     return dispatch_kernel(vt, dm, di.dim, [&](auto t, auto d, auto c) {
         using T = typename decltype(t)::type;
         constexpr int DM = decltype(d)::value, DC = decltype(c)::value;
         size_t lds = truth_lds_layout(di.dim, sizeof(T), k).total;
         hipLaunchKernelGGL((truth_kernel<T, DM, DC>), dim3(nq), dim3(64),
-                           lds, (hipStream_t)stream, di, queries, nq, k, ov, od);
+                           lds, nullptr, di, queries, nq, k, ov, od);
         return (int)hipGetLastError();
     });
 }

@@ -7,7 +7,7 @@ under tests/golden/dist_pairs_*.bin, at every dim of the list, through
 `Truth`: the pairs' y vectors are index rows, the x vectors the queries.
 
 Part 2 runs the search kernels (batched LDS-heap and global-heap, KDT,
-iterator, speculation) at the dims that no golden fixture reaches, on
+iterator) at the dims that no golden fixture reaches, on
 seeded CPU-built indexes, bit-exactly against the oracle. MaxCheck is 512,
 but 1100 where the global-heap kernel has to be forced. Its CPU sibling
 checks that those indexes are searchable at all, so that the comparison
@@ -124,9 +124,7 @@ KDT_CASES = [("KDT", "f32", 128, "L2"), ("KDT", "f32", 768, "Cosine"),
              ("KDT", "f32", 31, "L2"), ("KDT", "i8", 64, "Cosine")]
 ITER_CASES = [("BKT", "f32", 128, "L2"), ("BKT", "f32", 31, "Cosine"),
               ("BKT", "f32", 768, "L2"), ("BKT", "i8", 260, "L2")]
-SPEC_CASES = [("BKT", "f32", 128, "L2"), ("BKT", "i8", 100, "Cosine")]
-ALL_CASES = sorted(set(BKT_CASES + GLOBAL_HEAP_CASES + KDT_CASES + ITER_CASES
-                       + SPEC_CASES))
+ALL_CASES = sorted(set(BKT_CASES + GLOBAL_HEAP_CASES + KDT_CASES + ITER_CASES))
 ITER_BATCHES = [8, 8, 8]
 
 _ref = {}
@@ -279,16 +277,3 @@ def test_gpu_iterator_at_dim(case):
     it = gpu_from_case(c).Iterate(c["q"], max_check=MC)
     assert_iter_calls_equal(it, calls, ITER_BATCHES, _id(case))
     it.Close()
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("case", SPEC_CASES, ids=_id)
-def test_gpu_speculation_at_dim(monkeypatch, case):
-    """SPTAG_AMD_SPEC=3 touches ceil(dim*esz/128) lines of a vector ahead of
-    its distance: 4 lines at float 128, one short line at int8 100."""
-    c, ov, od = _checked_case(case)
-    ix = gpu_from_case(c)
-    monkeypatch.setenv("SPTAG_AMD_SPEC", "3")
-    gv, gd = ix.BatchSearch(c["q"], K, MC)
-    np.testing.assert_array_equal(gv, ov)
-    np.testing.assert_array_equal(_bits(gd), _bits(od))
