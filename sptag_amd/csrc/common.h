@@ -50,7 +50,9 @@ struct SearchCfg {
 
 enum { PROF_STATS = 16 };  /* stats stride (int32) in prof mode; slots:
     0 checked, 1 popped, 2 seed, 3 pop, 4 row, 5 serial, 6 cas, 7 dist,
-    8 insert, 9 tree, 10 epilogue (cycles), 11 NG-insert share of 8 */
+    8 insert, 9 tree, 10 epilogue (cycles), 11 NG-insert share of 8; inside
+    2 + 9: 12 tree-heap inserts, 13 tree-heap pops, 14 SearchTrees leaf
+    branch (visited CAS + NG insert) */
 
 /* per-launch buffers */
 struct SearchBufs {
@@ -189,5 +191,32 @@ int launch_merge_topk(const int32_t* vids, const float* dists,
                       const MergeBases& bases, int nshards, int32_t nq,
                       int32_t k_in, int32_t k_out, int32_t* out_vids,
                       float* out_dists);
+
+/* heap probe (tests/test_gpu_heap_ops.py): a script of nops heap operations
+ * (ops[i] != 0: insert {nodes[i], dists[i]}; 0: pop) on a heap of capacity
+ * `cap` whose entries [0..lsplit] sit in LDS (lsplit 0: none), run once with
+ * the serial heap functions (block 0) and once with the wave-wide ones
+ * (block 1). All pointers are device memory: heaps [2][cap+1] entries of
+ * {int32 node, float distance}, pops [2][nops] entries (written at pop ops
+ * only), final [2] x {count, overflow flag}, zeroed by the caller. */
+enum { HEAP_PROBE_MAX_CAP = 1 << 20, HEAP_PROBE_MAX_LSPLIT = 4095 };
+struct HeapProbeArgs {
+    int32_t cap, ref_cap, lsplit, nops;
+    const int32_t* ops;
+    const int32_t* nodes;
+    const float* dists;
+    void* heaps;
+    void* pops;
+    int32_t* final;
+};
+int launch_heap_probe(const HeapProbeArgs& args);
+
+/* host entry of the probe, all pointers host memory; exported for the tests
+ * and deliberately not part of include/sptag_amd.h */
+extern "C" int sptagamd_dbg_heap_probe(int device, int32_t cap, int32_t ref_cap,
+                                       int32_t lsplit, int32_t nops, const int32_t* ops,
+                                       const int32_t* nodes, const float* dists,
+                                       void* out_heaps, void* out_pops,
+                                       int32_t* out_final);
 
 }  /* namespace sptag_amd */

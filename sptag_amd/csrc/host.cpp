@@ -566,6 +566,16 @@ static void prof_dump(const PassOut& out, int32_t nq, double ms)
     for (int32_t i = 0; i < nq; i++)
         ngi += (double)out.stats[(size_t)out.sstride * i + 2 + NPHASE];
     fprintf(stderr, "  (insert = ng-heap %14.0f + results-set rest)\n", ngi);
+    /* inside seed + tree: the tree heap's inserts and pops, and the leaf
+     * branch of SearchTrees (visited CAS + NG insert) */
+    static const char* aname[3] = {"spt-insert", "spt-pop", "leaf"};
+    for (int a = 0; a < 3; a++) {
+        double t = 0;
+        for (int32_t i = 0; i < nq; i++)
+            t += (double)out.stats[(size_t)out.sstride * i + 3 + NPHASE + a];
+        fprintf(stderr, "  (seed+tree: %-10s %14.0f  (%5.1f%%))\n", aname[a], t,
+                all > 0 ? 100.0 * t / all : 0.0);
+    }
 }
 
 /* core search on DEVICE buffers; scratch cached on the handle. */
@@ -1546,3 +1556,42 @@ int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries, int32_t nq,
 }
 
 }  /* extern "C" */
+
+/* heap probe (common.h): upload the script, run both forms, download */
+extern "C" int sptagamd_dbg_heap_probe(int device, int32_t cap, int32_t ref_cap, int32_t lsplit,
+                            int32_t nops, const int32_t* ops, const int32_t* nodes,
+                            const float* dists, void* out_heaps, void* out_pops,
+                            int32_t* out_final)
+{
+    using namespace sptag_amd;
+    if (!ops || !nodes || !dists || !out_heaps || !out_pops || !out_final ||
+        cap < 1 || cap > HEAP_PROBE_MAX_CAP || ref_cap < cap || lsplit < 0 ||
+        lsplit > HEAP_PROBE_MAX_LSPLIT || nops < 1)
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    const size_t hbytes = 2 * ((size_t)cap + 1) * 8, pbytes = 2 * (size_t)nops * 8;
+    DevBuf d_ops, d_nodes, d_dists, d_heaps, d_pops, d_final;
+    int rc;
+    if ((rc = dev_upload(d_ops, ops, (size_t)nops * 4)) != SPTAG_AMD_OK) return rc;
+    if ((rc = dev_upload(d_nodes, nodes, (size_t)nops * 4)) != SPTAG_AMD_OK) return rc;
+    if ((rc = dev_upload(d_dists, dists, (size_t)nops * 4)) != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(d_heaps.alloc(hbytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_pops.alloc(pbytes), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_final.alloc(16), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(hipMemset(d_heaps.as(), 0xff, hbytes), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemset(d_pops.as(), 0xff, pbytes), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemset(d_final.as(), 0, 16), SPTAG_AMD_ERR_NOGPU);
+    HeapProbeArgs a{cap, ref_cap, lsplit, nops, d_ops.as<int32_t>(),
+                    d_nodes.as<int32_t>(), d_dists.as<float>(), d_heaps.as(),
+                    d_pops.as(), d_final.as<int32_t>()};
+    if (launch_heap_probe(a) != 0) return SPTAG_AMD_ERR_INTERNAL;
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_heaps, d_heaps.as(), hbytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_pops, d_pops.as(), pbytes, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_final, d_final.as(), 16, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}

@@ -14,8 +14,11 @@
  * the oracle/_ref build (see oracle/sptag_oracle.c).
  *
  * Division of labor inside the wave:
- *   - heap/result-set mutation is inherently serial (pop order on equal
- *     keys is part of the parity contract) -> lane 0, state in LDS;
+ *   - frontier/tree heaps: the reference's binary heap, comparison for
+ *     comparison (pop order on equal keys is part of the parity contract),
+ *     evaluated by the whole wave in the batched search (ndheap_*_wave) and
+ *     by lane 0 where inserts interleave with other serial work; result-set
+ *     mutation -> lane 0, state in LDS;
  *   - adjacency row load: lanes 0..deg-1, one coalesced 128B line;
  *   - visited-set: per-query open-addressing table in GLOBAL memory
  *     (512KB-class tables do not fit LDS at MaxCheck 8192 — SURVEY.md §7),
@@ -38,6 +41,13 @@
 namespace sptag_amd {
 
 #define DEV __device__ __forceinline__
+
+#ifndef SPTAG_LB_WAVES
+#define SPTAG_LB_WAVES 1   /* min waves/SIMD hint; raise to cap VGPRs */
+#endif
+#ifndef SPTAG_WAVE_POP
+#define SPTAG_WAVE_POP 1   /* 0: serial frontier/tree pops (measurement builds) */
+#endif
 
 static constexpr float MAXDIST = __FLT_MAX__ / 10.0f; /* Common.h:122 */
 
@@ -70,13 +80,14 @@ struct HeapRef {
 
 DEV NodeDist hget(const HeapRef& h, int i)
 {
-    return (h.lds && i <= h.lsplit) ? h.lds[i] : h.a[i];
+    /* unsigned index: the global access is base + 32-bit offset */
+    return (h.lds && i <= h.lsplit) ? h.lds[(uint32_t)i] : h.a[(uint32_t)i];
 }
 
 DEV void hset(const HeapRef& h, int i, NodeDist v)
 {
-    if (h.lds && i <= h.lsplit) h.lds[i] = v;
-    else h.a[i] = v;
+    if (h.lds && i <= h.lsplit) h.lds[(uint32_t)i] = v;
+    else h.a[(uint32_t)i] = v;
 }
 
 /* Heap.h:38-62 insert (incl. the full-heap last-level replace path). */
@@ -152,6 +163,140 @@ DEV NodeDist ndheap_pop(HeapRef h, int* count)
 
 DEV NodeDist ndheap_top(HeapRef h, int count) { return count == 0 ? hget(h, 0) : hget(h, 1); }
 
+/* ------------------------------------------------------------------ *
+ * the same heap, evaluated by the whole wave: same comparisons on the
+ * same array, so the array after every operation is the serial one's
+ * ------------------------------------------------------------------ */
+
+/* v broadcast from lane l (wave-uniform l) */
+DEV float lane_bcast(float v, int l)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+DEV NodeDist lane_bcast(NodeDist v, int l)
+{
+    return NodeDist{__builtin_amdgcn_readlane(v.node, l), lane_bcast(v.distance, l)};
+}
+
+/* Orders one wave-wide heap operation against the next, which reads what
+ * this one wrote through other lanes, in LDS or in the global tail. A block
+ * is exactly one wave, and a wave's LDS operations, and its vector memory
+ * operations, are each carried out in the order they were issued (AMDGPU
+ * memory model: a wavefront-scope release/acquire needs no wait and no
+ * cache action on gfx9xx; an index lives in one of the two storages for
+ * good). What the fence has to stop is the compiler moving or forwarding
+ * accesses across it, so the stores of an insert are not waited for. */
+DEV void heap_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+/* ndheap_insert by all 64 lanes; v and count are wave-uniform. The ancestors
+ * of the slot are loc>>1, loc>>2, .., 1, known before the first comparison;
+ * the serial loop passes those v is strictly below, moving each down one
+ * step, and stops at the first it is not. No ancestor is written before it
+ * is read, so lane j reads ancestor j+1, a ballot finds the stop level, and
+ * lane j writes level j: its ancestor below the stop, v at it. */
+DEV void ndheap_insert_wave(HeapRef h, int& count, NodeDist v, int* oflow)
+{
+    const int lane = threadIdx.x;
+    int loc;
+    if (count == h.cap) {
+        if (h.cap < h.ref_cap) {
+            if (lane == 0) *oflow = 1;
+            return;
+        }
+        /* only where a heap sits at the reference's capacity: lane 0 scans */
+        int maxi = 0;
+        float maxd = 0.0f;
+        if (lane == 0) {
+            int lastlevel = heap_lastlevel(h.cap);
+            maxi = lastlevel;
+            maxd = hget(h, maxi).distance;
+            for (int i = lastlevel + 1; i <= h.cap; i++) {
+                float di = hget(h, i).distance;
+                if (maxd < di) { maxi = i; maxd = di; }
+            }
+        }
+        maxi = __builtin_amdgcn_readfirstlane(maxi);
+        maxd = lane_bcast(maxd, 0);
+        if (v.distance > maxd) return;
+        loc = maxi;
+    } else {
+        loc = ++count;
+    }
+    const int nanc = 31 - __clz(loc);       /* ancestors of loc; < 32 */
+    NodeDist p = v;
+    bool below = false;
+    if (lane < nanc) {
+        p = hget(h, loc >> (lane + 1));
+        below = v.distance < p.distance;
+    }
+    const int stop = __builtin_ctzll(__ballot(!below));   /* <= nanc */
+    if (lane <= stop) hset(h, loc >> lane, lane == stop ? v : p);
+    heap_fence();
+}
+
+/* ndheap_pop by all 64 lanes; count is wave-uniform, the old top comes back
+ * on every lane. The sinking value (the old last entry) follows the
+ * smaller-child path, left on ties, and stops at the first child that is not
+ * strictly below it; children are read before anything under them is
+ * written. The wave loads the path's surroundings a block at a time: lane l
+ * >= 2 holds the descendant of the block's root r whose index relative to r
+ * is l (five levels, 62 entries; lanes past the count hold nothing), the
+ * walk inside the block runs on wave-uniform indexes with readlane, every
+ * entry on the path is then written to its parent's index by the lane that
+ * holds it, and lane 0 writes the sunk value where the walk stopped. The
+ * first block also brings the old top (lane 1) and the old last entry
+ * (lane 0) in the same read. */
+DEV NodeDist ndheap_pop_wave(HeapRef h, int& count)
+{
+    const int lane = threadIdx.x;
+    if (count == 0) return hget(h, 0);
+    const uint32_t n = (uint32_t)count - 1;      /* entries left */
+    /* lane l >= 1 is `off` entries into level `d` under the block's root */
+    const int d = lane ? 31 - __clz(lane) : 0;
+    const int off = lane - (1 << d);
+    uint32_t r = 1;
+    uint32_t gi = lane == 0 ? (uint32_t)count : (r << d) + off;
+    NodeDist val{0, 0.0f};
+    if (lane <= 1 || gi <= n) val = hget(h, (int)gi);
+    const NodeDist pv = lane_bcast(val, 0);
+    const NodeDist top = lane_bcast(val, 1);
+    /* the vacated slot beyond count is dead until the next insert writes it */
+    count = (int)n;
+    if (n == 0) return top;
+    for (;;) {
+        int p = 1;                  /* relative index the sinking value is at */
+        uint64_t path = 0;          /* relative indexes that move up one level */
+        bool stopped = false;
+#pragma unroll
+        for (int lvl = 1; lvl <= 5; lvl++) {
+            int cr = p << 1;
+            uint32_t gc = (r << lvl) + (uint32_t)(cr - (1 << lvl));
+            if (gc > n) { stopped = true; break; }
+            NodeDist nv = lane_bcast(val, cr);
+            if (gc < n) {
+                NodeDist nv2 = lane_bcast(val, cr + 1);
+                if (nv.distance > nv2.distance) { cr++; nv = nv2; }
+            }
+            if (!(nv.distance < pv.distance)) { stopped = true; break; }
+            path |= 1ull << cr;
+            p = cr;
+        }
+        const int dp = 31 - __clz(p);
+        const uint32_t gp = (r << dp) + (uint32_t)(p - (1 << dp));
+        const bool onpath = (path >> lane) & 1;
+        if (onpath || (stopped && lane == 0))
+            hset(h, (int)(onpath ? gi >> 1 : gp), onpath ? val : pv);
+        if (stopped) break;
+        /* the next block is strictly below everything written so far */
+        r = gp;
+        gi = (r << d) + off;
+        if (lane >= 2 && gi <= n) val = hget(h, (int)gi);
+    }
+    heap_fence();
+    return top;
+}
+
 /* DistPriorityQueue (WorkSpace.h:167-225): 1-based bounded float max-heap
  * seeded with MaxDist; len starts at 1. */
 DEV int dpq_insert(float* a, int* len, int cap, float dist)
@@ -181,12 +326,6 @@ DEV int dpq_insert(float* a, int* len, int cap, float dist)
         a[next] = dist;
     }
     return 1;
-}
-
-/* v broadcast from lane l (wave-uniform l) */
-DEV float lane_bcast(float v, int l)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
 /* DistPriorityQueue (WorkSpace.h:167-225) for one whole adjacency row, wave-
@@ -501,6 +640,41 @@ DEV float ref_dist_grp(const T* q, const T* v, int d)
         return ref_dist_grp_i8<DM>((const int8_t*)q, (const int8_t*)v, d);
 }
 
+/* Per-phase cycle marks, diagnostic builds only; every member is empty
+ * without PROF. One wave per workgroup, so lane-0 clock64 spans are
+ * wave-accurate. */
+template <bool PROF>
+struct PhaseClock {
+    uint64_t pc[9] = {};
+    uint64_t t = 0, ng = 0, t_ng = 0;
+    uint64_t aux[3] = {}, t_aux = 0;
+    DEV void mark() { if (PROF && threadIdx.x == 0) t = clock64(); }
+    DEV void acc(int i)
+    {
+        if (PROF && threadIdx.x == 0) {
+            uint64_t now = clock64();
+            pc[i] += now - t;
+            t = now;
+        }
+    }
+    /* lane 0 only: NG-insert share of the `insert` phase */
+    DEV void ng_begin() { if (PROF) t_ng = clock64(); }
+    DEV void ng_end() { if (PROF) ng += clock64() - t_ng; }
+    /* lane 0 only, inside a phase: 0 SPT inserts, 1 SPT pops, 2 leaf branch
+     * of search_trees_dev (visited CAS + NG insert) */
+    DEV void aux_begin() { if (PROF) t_aux = clock64(); }
+    DEV void aux_end(int i) { if (PROF) aux[i] += clock64() - t_aux; }
+    DEV void store(int32_t* s) const   /* stats slots 2..15 */
+    {
+#pragma unroll
+        for (int i = 0; i < 9; i++) s[2 + i] = (int32_t)pc[i];
+        s[11] = (int32_t)ng;
+#pragma unroll
+        for (int i = 0; i < 3; i++) s[12 + i] = (int32_t)aux[i];
+        s[15] = 0;
+    }
+};
+
 /* ------------------------------------------------------------------ *
  * per-query context
  * ------------------------------------------------------------------ */
@@ -722,59 +896,92 @@ DEV void stage_child_dists(QCtx<T>& c, int base, int cnt)
     if constexpr (TOUCH) asm volatile("" :: "v"(ts));
 }
 
-/* One chunk of a BKT node's children into the SPT heap (lane 0 inserts). */
-template <typename T, int DM, int DC>
-DEV void stage_children(QCtx<T>& c, int base, int cnt)
+/* wave-uniform read of a counter that lane 0 keeps in LDS */
+DEV int uniform_count(const int* p) { return __builtin_amdgcn_readfirstlane(*p); }
+
+/* Pop heap `h`, whose count lane 0 keeps at *pcount; the old top comes back
+ * on every lane. The serial form (SPTAG_WAVE_POP=0, measurement builds) goes
+ * through ss->popped and a barrier. */
+DEV NodeDist pop_frontier(HeapRef h, int* pcount, SerialState* ss)
+{
+#if SPTAG_WAVE_POP
+    int n = uniform_count(pcount);
+    NodeDist top = ndheap_pop_wave(h, n);
+    if (threadIdx.x == 0) *pcount = n;
+    return top;
+#else
+    if (threadIdx.x == 0) ss->popped = ndheap_pop(h, pcount);
+    __syncthreads();
+    return ss->popped;
+#endif
+}
+
+/* One chunk of a BKT node's children into the SPT heap: cnt wave-wide
+ * inserts back to back, child i's distance taken from lane i. */
+template <typename T, int DM, int DC, bool PROF>
+DEV void stage_children(QCtx<T>& c, int base, int cnt, PhaseClock<PROF>& clk)
 {
     stage_child_dists<T, DM, DC, true>(c, base, cnt);
-    heap_warm_parents(c.spt, c.ss->spt_count, cnt);
-    if (c.lane == 0)
-        for (int i = 0; i < cnt; i++)
-            ndheap_insert(c.spt, &c.ss->spt_count,
-                          NodeDist{base + i, c.dstage[i]}, &c.ss->oflow);
+    int n = uniform_count(&c.ss->spt_count);
+    heap_warm_parents(c.spt, n, cnt);
+    const float dv = c.lane < cnt ? c.dstage[c.lane] : MAXDIST;
+    clk.aux_begin();
+    for (int i = 0; i < cnt; i++)
+        ndheap_insert_wave(c.spt, n, NodeDist{base + i, lane_bcast(dv, i)}, &c.ss->oflow);
+    clk.aux_end(0);
+    if (c.lane == 0) c.ss->spt_count = n;
     __syncthreads();
 }
 
-/* BKTree.h:772 SearchTrees — wave-cooperative, serial decisions on lane 0. */
-template <typename T, int DM, int DC>
-DEV void search_trees_dev(QCtx<T>& c, int limit)
+/* A tree node's center joins the NG frontier unless it was visited: lane 0
+ * claims it in the visited table, the wave inserts. Returns 1 if it went in. */
+template <typename T>
+DEV int frontier_add_center(QCtx<T>& c, int32_t center, float dist)
+{
+    int seen = 1;
+    if (c.lane == 0) seen = visited_test_insert(c.vtab, c.vmask, center, &c.ss->oflow);
+    if (__builtin_amdgcn_readfirstlane(seen)) return 0;
+    int n = uniform_count(&c.ss->ng_count);
+    ndheap_insert_wave(c.ng, n, NodeDist{center, dist}, &c.ss->oflow);
+    if (c.lane == 0) c.ss->ng_count = n;
+    return 1;
+}
+
+/* BKTree.h:772 SearchTrees — the whole wave pops, inserts and expands; lane 0
+ * keeps the counters. Every counter read here follows a barrier that follows
+ * its last write. */
+template <typename T, int DM, int DC, bool PROF>
+DEV void search_trees_dev(QCtx<T>& c, int limit, PhaseClock<PROF>& clk)
 {
     const DevIndex& di = *c.di;
     for (;;) {
         __syncthreads();
         if (c.ss->spt_count <= 0 || c.ss->oflow) break;
-        if (c.lane == 0) c.ss->popped = ndheap_pop(c.spt, &c.ss->spt_count);
-        __syncthreads();
-        NodeDist bcell = c.ss->popped;
+        clk.aux_begin();
+        NodeDist bcell = pop_frontier(c.spt, &c.ss->spt_count, c.ss);
+        clk.aux_end(1);
         int32_t center = di.tree_nodes[(size_t)bcell.node * 3 + 0];
         int32_t cs = di.tree_nodes[(size_t)bcell.node * 3 + 1];
         int32_t ce = di.tree_nodes[(size_t)bcell.node * 3 + 2];
         if (cs < 0) {
-            if (c.lane == 0) {
-                if (!visited_test_insert(c.vtab, c.vmask, center, &c.ss->oflow)) {
-                    c.ss->checked++;
-                    ndheap_insert(c.ng, &c.ss->ng_count, NodeDist{center, bcell.distance}, &c.ss->oflow);
-                }
-                c.ss->break_flag = (c.ss->checked >= limit);
-            }
-            __syncthreads();
-            if (c.ss->break_flag) break;
+            clk.aux_begin();
+            const int checked = uniform_count(&c.ss->checked) +
+                                frontier_add_center(c, center, bcell.distance);
+            if (c.lane == 0) c.ss->checked = checked;
+            clk.aux_end(2);
+            if (checked >= limit) break;
         } else {
-            if (c.lane == 0) {
-                if (!visited_test_insert(c.vtab, c.vmask, center, &c.ss->oflow)) {
-                    ndheap_insert(c.ng, &c.ss->ng_count, NodeDist{center, bcell.distance}, &c.ss->oflow);
-                }
-            }
+            frontier_add_center(c, center, bcell.distance);
             for (int base = cs; base < ce; base += 64)
-                stage_children<T, DM, DC>(c, base, min(64, ce - base));
+                stage_children<T, DM, DC>(c, base, min(64, ce - base), clk);
         }
     }
     __syncthreads();
 }
 
 /* BKTree.h:697 InitSearchTrees (m_bfs = 0). */
-template <typename T, int DM, int DC>
-DEV void init_search_trees_dev(QCtx<T>& c)
+template <typename T, int DM, int DC, bool PROF>
+DEV void init_search_trees_dev(QCtx<T>& c, PhaseClock<PROF>& clk)
 {
     const DevIndex& di = *c.di;
     for (int t = 0; t < di.ntrees; t++) {
@@ -783,15 +990,16 @@ DEV void init_search_trees_dev(QCtx<T>& c)
         int32_t cs = di.tree_nodes[(size_t)root * 3 + 1];
         int32_t ce = di.tree_nodes[(size_t)root * 3 + 2];
         if (cs < 0) {
-            if (c.lane < 16) {
-                float dv = ref_dist_grp<T, DM, DC>(c.qlds, vec_at<T>(di, center), di.dim);
-                if (c.lane == 0)
-                    ndheap_insert(c.spt, &c.ss->spt_count, NodeDist{root, dv}, &c.ss->oflow);
-            }
+            float dv = 0.0f;
+            if (c.lane < 16)
+                dv = ref_dist_grp<T, DM, DC>(c.qlds, vec_at<T>(di, center), di.dim);
+            int n = uniform_count(&c.ss->spt_count);
+            ndheap_insert_wave(c.spt, n, NodeDist{root, lane_bcast(dv, 0)}, &c.ss->oflow);
+            if (c.lane == 0) c.ss->spt_count = n;
             __syncthreads();
         } else {
             for (int base = cs; base < ce; base += 64)
-                stage_children<T, DM, DC>(c, base, min(64, ce - base));
+                stage_children<T, DM, DC>(c, base, min(64, ce - base), clk);
         }
     }
 }
@@ -842,40 +1050,11 @@ DEV int expand_neighbors(QCtx<T>& c, const Row& r)
  * main search kernel
  * ------------------------------------------------------------------ */
 
-#ifndef SPTAG_LB_WAVES
-#define SPTAG_LB_WAVES 1   /* min waves/SIMD hint; raise to cap VGPRs */
-#endif
 
-/* Per-phase cycle marks, diagnostic builds only; every member is empty
- * without PROF. One wave per workgroup, so lane-0 clock64 spans are
- * wave-accurate. */
-template <bool PROF>
-struct PhaseClock {
-    uint64_t pc[9] = {};
-    uint64_t t = 0, ng = 0, t_ng = 0;
-    DEV void mark() { if (PROF && threadIdx.x == 0) t = clock64(); }
-    DEV void acc(int i)
-    {
-        if (PROF && threadIdx.x == 0) {
-            uint64_t now = clock64();
-            pc[i] += now - t;
-            t = now;
-        }
-    }
-    /* lane 0 only: NG-insert share of the `insert` phase */
-    DEV void ng_begin() { if (PROF) t_ng = clock64(); }
-    DEV void ng_end() { if (PROF) ng += clock64() - t_ng; }
-    DEV void store(int32_t* s) const   /* stats slots 2..15 */
-    {
-#pragma unroll
-        for (int i = 0; i < 9; i++) s[2 + i] = (int32_t)pc[i];
-        s[11] = (int32_t)ng;
-        s[12] = s[13] = s[14] = s[15] = 0;
-    }
-};
-
+/* The small class is held to the 7 waves/SIMD step (72 VGPRs) by hint; it
+ * allocates 70 without scratch (profiles/wave_heaps_kernel_resources.txt). */
 template <typename T, int DM, int DC, bool LDSHEAP, bool PROF = false>
-__global__ __launch_bounds__(64, SPTAG_LB_WAVES)
+__global__ __launch_bounds__(64, (DC == DC_SMALL && !PROF && SPTAG_LB_WAVES < 7) ? 7 : SPTAG_LB_WAVES)
 void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
 {
     const int q = blockIdx.x;
@@ -900,9 +1079,9 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     float dmax = MAXDIST;
 
     clk.mark();
-    init_search_trees_dev<T, DM, DC>(c);
+    init_search_trees_dev<T, DM, DC>(c, clk);
     __syncthreads();
-    search_trees_dev<T, DM, DC>(c, cfg.init_pivots);
+    search_trees_dev<T, DM, DC>(c, cfg.init_pivots, clk);
     clk.acc(0);
 
     int popped = 0;
@@ -911,11 +1090,9 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         __syncthreads();
         if (ss->ng_count <= 0 || ss->terminate || ss->oflow) break;
         clk.mark();
-        if (lane == 0) ss->popped = ndheap_pop(c.ng, &ss->ng_count);
-        __syncthreads();
+        const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count, ss);
         clk.acc(1);
         popped++;
-        NodeDist gnode = ss->popped;
         const Row row = load_row(c, gnode.node);
         clk.acc(2);
 
@@ -965,21 +1142,21 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
          * candidates m_Results accepts is decided once, wave-wide, from the
          * set at the start of the pop (dpq_accept_row); nothing between two
          * NG inserts depends on the set any more. The NG frontier heap stays
-         * an exact Heap.h emulation on lane 0 (its pop order on equal keys
-         * is part of the parity contract): the accepted candidates go in
-         * row order, back to back. Nothing reads `checked` inside a row. */
-        const uint64_t acc = dpq_accept_row(
-            dpq, cfg.dpq_cap, ncand, lane < ncand ? c.dstage[lane] : MAXDIST, dmax);
-        heap_warm_parents(c.ng, ss->ng_count, __popcll(acc));
+         * an exact Heap.h emulation (its pop order on equal keys is part of
+         * the parity contract), evaluated by the whole wave: the accepted
+         * candidates go in row order, back to back, each taken from the lane
+         * that holds it. Nothing reads `checked` inside a row. */
+        const NodeDist cand{lane < ncand ? c.istage[lane] : -1,
+                            lane < ncand ? c.dstage[lane] : MAXDIST};
+        const uint64_t acc = dpq_accept_row(dpq, cfg.dpq_cap, ncand, cand.distance, dmax);
+        int ngc = uniform_count(&ss->ng_count);
+        clk.ng_begin();
+        for (uint64_t m = acc; m; m &= m - 1)
+            ndheap_insert_wave(c.ng, ngc, lane_bcast(cand, __builtin_ctzll(m)), &ss->oflow);
+        clk.ng_end();
         if (lane == 0) {
             ss->checked += ncand;
-            clk.ng_begin();
-            for (uint64_t m = acc; m; m &= m - 1) {
-                int r = __builtin_ctzll(m);
-                ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], c.dstage[r]},
-                              &ss->oflow);
-            }
-            clk.ng_end();
+            ss->ng_count = ngc;
             /* dynamic pivots (BKTIndex.cpp:346-349) */
             ss->want_tree = (ndheap_top(c.ng, ss->ng_count).distance >
                              ndheap_top(c.spt, ss->spt_count).distance);
@@ -987,7 +1164,7 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         __syncthreads();
         clk.acc(6);
         if (ss->want_tree)
-            search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked);
+            search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked, clk);
         clk.acc(7);
     }
     __syncthreads();
@@ -1051,10 +1228,11 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
     SerialState* ss = c.ss;
     QRes* qrs = c.qrs;
 
+    PhaseClock<false> clk;
     if (st.first) {
-        init_search_trees_dev<T, DM, DC>(c);
+        init_search_trees_dev<T, DM, DC>(c, clk);
         __syncthreads();
-        search_trees_dev<T, DM, DC>(c, cfg.init_pivots);
+        search_trees_dev<T, DM, DC>(c, cfg.init_pivots, clk);
     }
 
     int count = 0;
@@ -1115,7 +1293,7 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
         }
         __syncthreads();
         if (ss->want_tree)
-            search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked);
+            search_trees_dev<T, DM, DC>(c, cfg.other_pivots + ss->checked, clk);
     }
     __syncthreads();
 
@@ -1487,6 +1665,63 @@ int launch_merge_topk(const int32_t* vids, const float* dists,
                        dim3(nq), dim3(64), staged ? (size_t)ncand * sizeof(MergeKey) : 0,
                        nullptr, vids, dists, bases, nshards, nq, k_in, k_out, out_vids,
                        out_dists);
+    return (int)hipGetLastError();
+}
+
+/* ------------------------------------------------------------------ *
+ * heap probe (tests): one script of inserts and pops on a HeapRef built
+ * from the arguments, run by block 0 with the serial functions and by
+ * block 1 with the wave-wide ones, each on its own array.
+ * ------------------------------------------------------------------ */
+
+__global__ __launch_bounds__(64)
+void heap_probe_kernel(HeapProbeArgs p)
+{
+    extern __shared__ char smem[];
+    const int lane = threadIdx.x;
+    const int b = blockIdx.x;
+    HeapRef h;
+    h.a = (NodeDist*)p.heaps + (size_t)b * (p.cap + 1);
+    h.lds = p.lsplit > 0 ? (NodeDist*)smem : nullptr;
+    h.lsplit = p.lsplit;
+    h.cap = p.cap;
+    h.ref_cap = p.ref_cap;
+    NodeDist* pops = (NodeDist*)p.pops + (size_t)b * p.nops;
+    int* oflow = p.final + b * 2 + 1;
+    int count = 0;
+    if (lane == 0) hset(h, 0, NodeDist{-1, MAXDIST});
+    __syncthreads();
+    if (b == 1) {
+        for (int i = 0; i < p.nops; i++) {
+            if (p.ops[i]) {
+                ndheap_insert_wave(h, count, NodeDist{p.nodes[i], p.dists[i]}, oflow);
+            } else {
+                NodeDist t = ndheap_pop_wave(h, count);
+                if (lane == 0) pops[i] = t;
+            }
+        }
+    } else if (lane == 0) {
+        for (int i = 0; i < p.nops; i++) {
+            if (p.ops[i]) ndheap_insert(h, &count, NodeDist{p.nodes[i], p.dists[i]}, oflow);
+            else pops[i] = ndheap_pop(h, &count);
+        }
+    }
+    __syncthreads();
+    if (lane == 0) p.final[b * 2] = count;
+    /* the caller reads the whole array from global memory */
+    if (h.lds)
+        for (int i = lane; i <= min(p.lsplit, p.cap); i += 64) h.a[i] = h.lds[i];
+}
+
+int launch_heap_probe(const HeapProbeArgs& p)
+{
+    /* the kernel indexes nothing outside these bounds */
+    if (p.cap < 1 || p.cap > HEAP_PROBE_MAX_CAP || p.ref_cap < p.cap || p.lsplit < 0 ||
+        p.lsplit > HEAP_PROBE_MAX_LSPLIT || p.nops < 1)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(heap_probe_kernel, dim3(2), dim3(64),
+                       p.lsplit > 0 ? ((size_t)p.lsplit + 1) * sizeof(NodeDist) : 0,
+                       nullptr, p);
     return (int)hipGetLastError();
 }
 
