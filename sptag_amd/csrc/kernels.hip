@@ -48,6 +48,19 @@ namespace sptag_amd {
 #ifndef SPTAG_WAVE_POP
 #define SPTAG_WAVE_POP 1   /* 0: serial frontier/tree pops (measurement builds) */
 #endif
+/* Loads that depend on nothing but the node a pop is about to return, issued
+ * ahead of that pop (peek_frontier). Bit mask, so that measurement builds can
+ * take the parts apart: 1 graph row, 2 tree triple. (4, the first chunk of a
+ * tree node's children's center ids, issued once the triple is in, was built
+ * and lost to the build without it: profiles/pop_ahead_bench.txt.) Serial
+ * pops go without. */
+#ifndef SPTAG_POP_AHEAD
+#define SPTAG_POP_AHEAD 3
+#endif
+#if !SPTAG_WAVE_POP
+#undef SPTAG_POP_AHEAD
+#define SPTAG_POP_AHEAD 0
+#endif
 
 static constexpr float MAXDIST = __FLT_MAX__ / 10.0f; /* Common.h:122 */
 
@@ -642,7 +655,10 @@ DEV float ref_dist_grp(const T* q, const T* v, int d)
 
 /* Per-phase cycle marks, diagnostic builds only; every member is empty
  * without PROF. One wave per workgroup, so lane-0 clock64 spans are
- * wave-accurate. */
+ * wave-accurate. With SPTAG_POP_AHEAD the `pop` span takes in the row's
+ * latency and the SPT-pop span the tree triple's, so `pop + row` and the
+ * seed / tree totals are what compare with a build without it, not the
+ * single lines. */
 template <bool PROF>
 struct PhaseClock {
     uint64_t pc[9] = {};
@@ -916,6 +932,18 @@ DEV NodeDist pop_frontier(HeapRef h, int* pcount, SerialState* ss)
 #endif
 }
 
+/* The node the next pop_frontier of `h` returns, wave-uniform; the heap is
+ * not empty. Index 1 is final once the last heap operation has been issued
+ * (heap_fence), so the loads whose address follows from this node alone can
+ * be issued ahead of the pop and come back under its own waits: vector
+ * memory loads return in the order they were issued, so the pop's wait for
+ * its next block covers them. The entry sits in the LDS tier where there is
+ * one, else in the line that the pop's first block reads. */
+DEV int32_t peek_frontier(const HeapRef& h)
+{
+    return __builtin_amdgcn_readfirstlane(hget(h, 1).node);
+}
+
 /* One chunk of a BKT node's children into the SPT heap: cnt wave-wide
  * inserts back to back, child i's distance taken from lane i. */
 template <typename T, int DM, int DC, bool PROF>
@@ -958,11 +986,24 @@ DEV void search_trees_dev(QCtx<T>& c, int limit, PhaseClock<PROF>& clk)
         __syncthreads();
         if (c.ss->spt_count <= 0 || c.ss->oflow) break;
         clk.aux_begin();
+#if SPTAG_POP_AHEAD & 2
+        /* the node about to be popped: its triple on lanes 0..2, issued
+         * ahead of the pop */
+        const int32_t* tn = di.tree_nodes + (size_t)peek_frontier(c.spt) * 3;
+        int32_t tri = 0;
+        if (c.lane < 3) tri = tn[c.lane];
+        NodeDist bcell = pop_frontier(c.spt, &c.ss->spt_count, c.ss);
+        clk.aux_end(1);
+        int32_t center = __builtin_amdgcn_readlane(tri, 0);
+        int32_t cs = __builtin_amdgcn_readlane(tri, 1);
+        int32_t ce = __builtin_amdgcn_readlane(tri, 2);
+#else
         NodeDist bcell = pop_frontier(c.spt, &c.ss->spt_count, c.ss);
         clk.aux_end(1);
         int32_t center = di.tree_nodes[(size_t)bcell.node * 3 + 0];
         int32_t cs = di.tree_nodes[(size_t)bcell.node * 3 + 1];
         int32_t ce = di.tree_nodes[(size_t)bcell.node * 3 + 2];
+#endif
         if (cs < 0) {
             clk.aux_begin();
             const int checked = uniform_count(&c.ss->checked) +
@@ -1015,17 +1056,32 @@ struct Row {
     int32_t checkNode;  /* last slot: < -1 marks a duplicate chain */
 };
 
+/* the load alone: this lane's slot of `node`'s row */
 template <typename T>
-DEV Row load_row(QCtx<T>& c, int32_t node)
+DEV int32_t load_row_lanes(QCtx<T>& c, int32_t node)
 {
     const int deg = c.di->deg;
     const int32_t* row = c.di->graph + (size_t)node * deg;
+    return c.lane < deg ? row[c.lane] : -1;
+}
+
+/* the row whose slots the lanes hold (first use of the loaded values) */
+template <typename T>
+DEV Row make_row(QCtx<T>& c, int32_t nn)
+{
+    const int deg = c.di->deg;
     Row r;
-    r.nn = c.lane < deg ? row[c.lane] : -1;
+    r.nn = nn;
     uint64_t negm = __ballot(c.lane >= deg || r.nn < 0);
     r.firstneg = negm ? (int)__builtin_ctzll(negm) : 64;
     r.checkNode = __shfl(r.nn, deg - 1);
     return r;
+}
+
+template <typename T>
+DEV Row load_row(QCtx<T>& c, int32_t node)
+{
+    return make_row(c, load_row_lanes(c, node));
 }
 
 /* neighbor expansion (BKTIndex.cpp:333-345): compact the unvisited
@@ -1090,10 +1146,19 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         __syncthreads();
         if (ss->ng_count <= 0 || ss->terminate || ss->oflow) break;
         clk.mark();
+#if SPTAG_POP_AHEAD & 1
+        /* the row of the node about to be popped, issued ahead of the pop */
+        const int32_t nn = load_row_lanes(c, peek_frontier(c.ng));
+        const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count, ss);
+        clk.acc(1);
+        popped++;
+        const Row row = make_row(c, nn);
+#else
         const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count, ss);
         clk.acc(1);
         popped++;
         const Row row = load_row(c, gnode.node);
+#endif
         clk.acc(2);
 
         if (lane == 0) {
