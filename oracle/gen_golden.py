@@ -188,6 +188,158 @@ def gen_cosine_add_goldens():
         print(f"cosine add golden {name}: {len(changed)} old rows changed")
 
 
+def read_bkt_tree(folder):
+    """(tree_start, nodes [nnodes, 3]: centerid, childStart, childEnd)."""
+    with open(os.path.join(folder, "tree.bin"), "rb") as f:
+        ntrees = np.frombuffer(f.read(4), dtype=np.int32)[0]
+        tstart = np.frombuffer(f.read(4 * ntrees), dtype=np.int32)
+        nnodes = np.frombuffer(f.read(4), dtype=np.int32)[0]
+        nodes = np.frombuffer(f.read(), dtype=np.int32).reshape(nnodes, 3)
+    return tstart, nodes
+
+
+def chain_layout(folder, dtype):
+    """The collapsed duplicate nodes of a saved BKT folder, checked.
+
+    A set of identical vectors larger than the leaf size becomes one tree
+    node with a negative childStart whose children are the copies
+    (BKTree.h:598-608); the representative's graph row carries
+    -2 - treeNode in its last slot (NeighborhoodGraph.h:395-400, :526) and
+    no graph row names a copy. One more member of the set is an ordinary
+    vector: k-means made it the centre of the cluster that then held nothing
+    but its copies, so it is the parent node's centerid, keeps its graph
+    edges and is found without the chain. Returns one dict per marker,
+    longest chain first: rep, node, copies (the children's ids, in tree
+    order), group (every id whose vector equals the representative's,
+    sorted) and stray (the group without rep and copies).
+
+    Asserts what the chain fixtures are for: at least three markers, each at
+    a node with childStart < -1; child counts above 64, from 11 to 64, and
+    above 3; no copy in any graph row; rep and copies all hold the same
+    vector."""
+    vec = read_default(os.path.join(folder, "vectors.bin"), dtype)
+    graph = read_default(os.path.join(folder, "graph.bin"), np.int32)
+    _, nodes = read_bkt_tree(folder)
+    deg = graph.shape[1]
+    reps = np.where(graph[:, deg - 1] < -1)[0]
+    assert len(reps) >= 3, f"{len(reps)} rows carry a marker"
+    chains = []
+    for rep in reps.tolist():
+        node = -2 - int(graph[rep, deg - 1])
+        assert 0 <= node < len(nodes)
+        cid, cs, ce = nodes[node].tolist()
+        assert cs < -1, f"marker of row {rep}: node {node} has childStart {cs}"
+        assert cid == rep and -cs < ce < len(nodes)
+        copies = nodes[-cs:ce, 0].copy()
+        group = np.where((vec == vec[rep]).all(axis=1))[0]
+        assert np.isin(copies, group).all() and rep not in copies
+        stray = np.setdiff1d(group, np.append(copies, rep))
+        chains.append({"rep": rep, "node": node, "copies": copies, "group": group,
+                       "stray": stray})
+    counts = [len(c["copies"]) for c in chains]
+    assert any(n > 64 for n in counts), counts
+    assert any(11 <= n <= 64 for n in counts), counts
+    assert sum(n > 3 for n in counts) >= 3, counts
+    allcopies = np.concatenate([c["copies"] for c in chains])
+    assert len(set(allcopies.tolist())) == len(allcopies)
+    assert not np.isin(graph, allcopies).any(), "a copy id appears in a graph row"
+    # rows other than the representatives end in a neighbour or -1
+    assert (np.delete(graph[:, deg - 1], reps) >= -1).all()
+    chains.sort(key=lambda c: -len(c["copies"]))
+    return chains
+
+
+CHAIN = {"f32_l2_chain": ("Float", "L2", 16, 20260),
+         "i8_cos_chain": ("Int8", "Cosine", 37, 20261)}
+CHAIN_BASE = 1270
+CHAIN_GROUPS = (70, 40, 20)        # rows 0, 1, 2 of the base, this many times each
+CHAIN_NQ = 32
+CHAIN_NADD = 16
+
+
+def gen_chain_goldens():
+    """Two small indexes that hold collapsed duplicate nodes, with what the
+    reference's own searcher, iterator and AddIndex return on them:
+      results_mc{512,2048}.bin  k = 10, the standard pair (meta.json)
+      results_k3_mc{512,2048}.bin    AddPoint rejects inside a chain
+      results_k100_mc{512,2048}.bin  a whole 70-chain fits; at MaxCheck 2048
+                                the frontier outgrows 256 entries, the
+                                smallest capacity a search can be held to
+      iter_b8_c5.bin            iterprobe, Next(8) x 5
+      iter_b64_c3.bin           iterprobe, Next(64) x 3: one call drains a
+                                chain into the frontier and returns from it
+      add16_vectors.bin, postadd16_graph.bin   f32_l2_chain only: 4 exact
+                                copies of chained vectors, 4 within 1e-3 of
+                                a representative, 8 random; the whole graph
+                                as the reference saved it after AddIndex
+    Queries: [0:3] near each chained vector, [3:6] equal to each, the rest
+    random. n is above 1000: below that BuildGraph returns before it writes
+    markers. Reachable on its own as `gen_golden.py chain`."""
+    import shutil
+    import tempfile
+    for name, (vtype, dist, dim, seed) in CHAIN.items():
+        rng = np.random.default_rng(seed)
+        if vtype == "Float":
+            dtype = np.float32
+            base = rng.random((CHAIN_BASE, dim), dtype=np.float32)
+            rand_q = rng.random((CHAIN_NQ - 6, dim), dtype=np.float32)
+            near = (base[:3] + np.float32(1e-3) *
+                    rng.standard_normal((3, dim)).astype(np.float32)).astype(np.float32)
+        else:
+            dtype = np.int8
+            base = rng.integers(-100, 101, (CHAIN_BASE, dim)).astype(np.int8)
+            rand_q = rng.integers(-100, 101, (CHAIN_NQ - 6, dim)).astype(np.int8)
+            near = base[:3].copy()
+            near[:, 0] += np.where(near[:, 0] < 0, 1, -1).astype(np.int8)
+        data = np.concatenate([base] + [np.repeat(base[g:g + 1], m - 1, axis=0)
+                                        for g, m in enumerate(CHAIN_GROUPS)])
+        data = data[rng.permutation(len(data))]
+        queries = np.concatenate([near, base[:3], rand_q])
+        assert data.shape[0] >= 1000 and queries.shape == (CHAIN_NQ, dim)
+        gen_fixture(name, data, queries, vtype, dist, maxchecks=[512, 2048], k=K)
+
+        d = os.path.join(GOLDEN, name)
+        idx = os.path.join(d, "index")
+        chains = chain_layout(idx, dtype)
+        print(f"{name}: markers at rows {[c['rep'] for c in chains]}, "
+              f"chains of {[len(c['copies']) for c in chains]} copies")
+        for k, mc in ((3, 512), (100, 512), (3, 2048), (100, 2048)):
+            run([os.path.join(REF, "indexsearcher"), "-d", str(dim), "-v", vtype,
+                 "-f", "DEFAULT", "-i", os.path.join(d, "queries.bin"), "-x", idx,
+                 "-k", str(k), "-m", str(mc), "-t", "2", "-of", "1",
+                 "-o", os.path.join(d, f"results_k{k}_mc{mc}.bin")])
+        for batch, calls in ((8, 5), (64, 3)):
+            run([os.path.join(REF, "iterprobe"), idx, os.path.join(d, "queries.bin"),
+                 str(batch), str(calls),
+                 os.path.join(d, f"iter_b{batch}_c{calls}.bin")])
+        if name != "f32_l2_chain":
+            continue
+
+        vec = read_default(os.path.join(idx, "vectors.bin"), dtype)
+        reps = [c["rep"] for c in chains]
+        add = np.concatenate([
+            vec[[reps[0], reps[0], reps[1], reps[2]]],
+            (vec[[reps[0], reps[1], reps[2], reps[0]]] + np.float32(1e-3) *
+             rng.standard_normal((4, dim)).astype(np.float32)).astype(np.float32),
+            rng.random((8, dim), dtype=np.float32)])
+        assert add.shape == (CHAIN_NADD, dim)
+        write_default(os.path.join(d, "add16_vectors.bin"), add)
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "postadd")
+            run([os.path.join(REF, "addprobe"), idx,
+                 os.path.join(d, "add16_vectors.bin"), out])
+            shutil.copy(os.path.join(out, "graph.bin"),
+                        os.path.join(d, "postadd16_graph.bin"))
+        before = read_default(os.path.join(idx, "graph.bin"), np.int32)
+        after = read_default(os.path.join(d, "postadd16_graph.bin"), np.int32)
+        assert after.shape == (before.shape[0] + CHAIN_NADD, before.shape[1])
+        assert (after[reps] != before[reps]).any(), "AddIndex changed no marker row"
+        np.testing.assert_array_equal(after[reps, -1], before[reps, -1])
+        assert (np.delete(after[:, -1], reps) >= -1).all()
+        print(f"{name}: AddIndex changed marker rows "
+              f"{[r for r in reps if (after[r] != before[r]).any()]}")
+
+
 # Distance pairs: every generic-form tail below 144, then the fixed-dim forms,
 # their neighbours and MAX_DIM; int8 up to 260, the largest admitted dim.
 DIST_DIMS_F32 = list(range(1, 145)) + [160, 192, 255, 256, 257, 384, 512, 513,
@@ -303,9 +455,11 @@ def main():
     gen_fixture("f32_l2_grid_ties", data, queries, "Float", "L2",
                 maxchecks=[512, 2048], k=3)
 
-    # 5. duplicate vectors — exercises the collapsed-center duplicate chain
-    #    (BKTIndex.cpp:292-312, BKTree.h:598-608): 2000 base vectors, each
-    #    repeated 4x.
+    # 5. duplicate vectors: 2000 base vectors, each repeated 4x. Many equal
+    #    distances, but a group of 4 fits a leaf, so nothing collapses and no
+    #    row carries a chain marker; the collapsed-center duplicate chain
+    #    (BKTIndex.cpp:292-312, BKTree.h:598-608) is what the chain fixtures
+    #    of gen_chain_goldens() are for.
     base = rng.random((2000, 16), dtype=np.float32)
     data = np.repeat(base, 4, axis=0)
     perm = rng.permutation(len(data))
@@ -359,10 +513,15 @@ def main():
     # 9. iterative + online-add golden answers
     gen_iter_and_add_goldens()
 
+    # 10. collapsed duplicate nodes and the chain walk
+    gen_chain_goldens()
+
 
 if __name__ == "__main__":
     if sys.argv[1:] == ["cosine-add"]:
         sys.exit(gen_cosine_add_goldens())
     if sys.argv[1:] == ["dist"]:
         sys.exit(gen_dist_goldens())
+    if sys.argv[1:] == ["chain"]:
+        sys.exit(gen_chain_goldens())
     sys.exit(main())

@@ -35,9 +35,11 @@ def _stream(calls, i):
 # ---- fixtures without an iterator golden --------------------------------
 
 def test_oracle_dups_stream_returns_duplicates():
-    """The duplicate chain (checkNode < -1) is only entered if duplicates
-    come out of the stream as separate results: every query must return an
-    id whose vector equals that of an id returned earlier."""
+    """Duplicates come out of the stream as separate results: every query
+    must return an id whose vector equals that of an id returned earlier.
+    They are ordinary graph neighbours here: a group of 4 fits a leaf, so
+    this fixture has no collapsed node and no chain marker (checkNode < -1);
+    the chain walk is tests/test_chain.py's."""
     g = load_golden("f32_l2_dups")
     vec = read_index_arrays(g["index"], np.float32)[0]
     calls = _golden_ref("f32_l2_dups", 8192, [8] * 5)

@@ -12,8 +12,9 @@ change, so every case compares ids and float bits with the oracle:
 - deleted vectors, and the f32_l2_dups fixture (every vector four times;
   built_case draws its own data, so the committed fixture, 8000 vectors of
   16 dims, stands in). Neither that fixture nor this project's builder
-  writes a chain marker into a row's last slot, so the chain walk itself is
-  reached by no test, here as before; the row's last slot is read as it was;
+  writes a chain marker into a row's last slot; the chain walk itself runs
+  in tests/test_chain.py, on indexes of the reference's builder that hold
+  collapsed duplicate nodes;
 - a frontier capacity that sends queries through the LDS pass and then the
   global-heap pass, where the peek is a global read;
 - one Next sequence of the iterator, whose tree heap is all in global memory.
