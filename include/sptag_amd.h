@@ -120,6 +120,20 @@ void sptag_amd_last_stats(SptagAmdIndex* idx, double* kernel_ms,
 int sptag_amd_truth(SptagAmdIndex* idx, const void* queries, int32_t nq,
                     int32_t k, int32_t* out_vids, float* out_dists);
 
+/* Exact search: sptag_amd_truth's answer, bit for bit (non-deleted rows,
+ * ascending (dist, vid), vid = -1 at MaxDist as padding, any k <= 1024),
+ * computed by the tiled kernels of exact.hip: a row read from HBM serves a
+ * tile of queries, int8 dots run on the matrix units, and the rows are cut
+ * into slices so that a small batch still fills the device. The tree and
+ * graph are not used. The _device form takes HIP device buffers, as
+ * sptag_amd_search_batch_device does. SPTAG_AMD_EXACT_SLICES=<1..64> in the
+ * environment overrides the number of slices (never the result). */
+int sptag_amd_exact_search(SptagAmdIndex* idx, const void* queries, int32_t nq,
+                           int32_t k, int32_t* out_vids, float* out_dists);
+int sptag_amd_exact_search_device(SptagAmdIndex* idx, const void* d_queries,
+                                  int32_t nq, int32_t k, int32_t* d_out_vids,
+                                  float* d_out_dists);
+
 /* Iterative (streaming) search — mirrors the reference's ResultIterator /
  * SearchIndexIterativeNext protocol (inc/Core/VectorIndex.h:43-49,
  * src/Core/ResultIterator.cpp) over a BATCH of nq per-query iterators whose
@@ -247,6 +261,10 @@ int sptag_amd_shards_search_batch_device(SptagAmdShards* set,
 int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries,
                            int32_t nq, int32_t k, int32_t* out_vids,
                            float* out_dists);
+/* The same over sptag_amd_exact_search per shard. */
+int sptag_amd_shards_exact_search(SptagAmdShards* set, const void* queries,
+                                  int32_t nq, int32_t k, int32_t* out_vids,
+                                  float* out_dists);
 int32_t sptag_amd_shards_count(const SptagAmdShards* set);
 /* sum of the shards' current vector counts */
 int64_t sptag_amd_shards_num_vectors(const SptagAmdShards* set);

@@ -72,6 +72,10 @@ def load_library():
     lib.sptag_amd_truth.restype = ctypes.c_int
     lib.sptag_amd_truth.argtypes = lib.sptag_amd_search_batch.argtypes[:4] + [
         ctypes.c_void_p, ctypes.c_void_p]
+    lib.sptag_amd_exact_search.restype = ctypes.c_int
+    lib.sptag_amd_exact_search.argtypes = lib.sptag_amd_truth.argtypes
+    lib.sptag_amd_exact_search_device.restype = ctypes.c_int
+    lib.sptag_amd_exact_search_device.argtypes = lib.sptag_amd_truth.argtypes
     lib.sptag_amd_save_index.restype = ctypes.c_int
     lib.sptag_amd_save_index.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     for f in ["num_vectors", "dim", "valuetype", "distmethod", "degree",
@@ -119,6 +123,8 @@ def load_library():
         lib.sptag_amd_search_batch.argtypes
     lib.sptag_amd_shards_truth.restype = ctypes.c_int
     lib.sptag_amd_shards_truth.argtypes = lib.sptag_amd_truth.argtypes
+    lib.sptag_amd_shards_exact_search.restype = ctypes.c_int
+    lib.sptag_amd_shards_exact_search.argtypes = lib.sptag_amd_truth.argtypes
     lib.sptag_amd_shards_count.restype = ctypes.c_int32
     lib.sptag_amd_shards_count.argtypes = [ctypes.c_void_p]
     lib.sptag_amd_shards_num_vectors.restype = ctypes.c_int64
@@ -315,6 +321,29 @@ class AnnIndex:
             raise SptagAmdError(rc, "truth")
         return vids, dists
 
+    def ExactSearch(self, queries, k):
+        """Exact top-k by the tiled brute-force kernels: Truth's answer, bit
+        for bit, at workload scale."""
+        queries = self._rows(queries)
+        nq = queries.shape[0]
+        vids = np.empty((nq, k), dtype=np.int32)
+        dists = np.empty((nq, k), dtype=np.float32)
+        rc = self._lib.sptag_amd_exact_search(
+            self._h, queries.ctypes.data_as(ctypes.c_void_p), nq, k,
+            vids.ctypes.data_as(ctypes.c_void_p),
+            dists.ctypes.data_as(ctypes.c_void_p))
+        if rc != 0:
+            raise SptagAmdError(rc, "exact_search")
+        return vids, dists
+
+    def ExactSearchDevice(self, d_queries_ptr, nq, k, d_vids_ptr, d_dists_ptr):
+        """ExactSearch on HIP device addresses, as BatchSearchDevice."""
+        rc = self._lib.sptag_amd_exact_search_device(
+            self._h, ctypes.c_void_p(d_queries_ptr), nq, k,
+            ctypes.c_void_p(d_vids_ptr), ctypes.c_void_p(d_dists_ptr))
+        if rc != 0:
+            raise SptagAmdError(rc, "exact_search_device")
+
     def Add(self, vectors, normalized=False):
         """Online add (reference AddIndex semantics below the tree-rebuild
         threshold); runs GPU refine searches per added vector."""
@@ -475,6 +504,11 @@ class ShardedIndex:
         """Exact brute-force top-k over all shards, global ids."""
         return self._call(self._lib.sptag_amd_shards_truth, "shards_truth",
                           queries, k)
+
+    def ExactSearch(self, queries, k):
+        """Truth's answer by AnnIndex.ExactSearch per shard."""
+        return self._call(self._lib.sptag_amd_shards_exact_search,
+                          "shards_exact_search", queries, k)
 
 
 class MetadataSet:

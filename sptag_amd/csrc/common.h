@@ -192,6 +192,17 @@ int launch_merge_topk(const int32_t* vids, const float* dists,
                       int32_t k_in, int32_t k_out, int32_t* out_vids,
                       float* out_dists);
 
+/* Exact search (exact.hip): a workgroup owns EXACT_QT queries and one slice
+ * of the rows; slice s of query q leaves a list of k entries, ascending
+ * (dist, vid) with a vid = -1 / MaxDist padding suffix, at [s][q] of
+ * lists_v/lists_d ([nslices][nq][k]), which launch_merge_topk merges with all
+ * bases 0. With one slice the lists are the answer. rows_per_slice is a
+ * multiple of EXACT_ROW_ALIGN, and nslices (<= MAX_SHARDS) of them cover n. */
+enum { EXACT_QT = 32, EXACT_ROW_ALIGN = 128 };
+int launch_exact(int valuetype, int distmethod, const DevIndex& di,
+                 const void* queries, int32_t nq, int32_t k, int32_t nslices,
+                 int32_t rows_per_slice, int32_t* lists_v, float* lists_d);
+
 /* heap probe (tests/test_gpu_heap_ops.py): a script of nops heap operations
  * (ops[i] != 0: insert {nodes[i], dists[i]}; 0: pop) on a heap of capacity
  * `cap` whose entries [0..lsplit] sit in LDS (lsplit 0: none), run once with

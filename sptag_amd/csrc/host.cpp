@@ -118,6 +118,8 @@ struct HostIndex {
     std::mutex lock;
     /* cached per-handle search scratch (grow-only) */
     DevBuf d_visited, d_oflow, d_stats, d_gng, d_gspt, d_redo, d_gspt0, d_gng0;
+    /* exact search: the per-slice lists, [slices][nq][k] (grow-only) */
+    DevBuf d_exact_v, d_exact_d;
     DevEvents ev;
     double last_kernel_ms = 0;
     long long last_checked = 0, last_popped = 0;
@@ -875,6 +877,95 @@ int sptag_amd_truth(SptagAmdIndex* ix, const void* queries, int32_t nq,
     return out.download(out_vids, out_dists, n);
 }
 
+/* How exact search cuts the rows: `slices` slices of `rows` rows each, rows a
+ * multiple of EXACT_ROW_ALIGN, none of them empty. `want` is the
+ * SPTAG_AMD_EXACT_SLICES override (tests force several slices at small n);
+ * without it there are enough slices for two workgroups per compute unit,
+ * as far as MAX_SHARDS, the row count and a 1 GiB bound on the lists allow. */
+struct ExactCut { int32_t slices, rows; };
+
+static ExactCut plan_exact(int32_t n, int32_t nq, int32_t k, int ncu, int want)
+{
+    const int64_t tiles = ((int64_t)n + EXACT_ROW_ALIGN - 1) / EXACT_ROW_ALIGN;
+    const int64_t qtiles = ((int64_t)nq + EXACT_QT - 1) / EXACT_QT;
+    int64_t s = want > 0 ? want : (2 * (int64_t)ncu + qtiles - 1) / qtiles;
+    if (want <= 0)
+        s = std::min(s, std::max<int64_t>(1, (1ll << 30) / ((int64_t)nq * k * 8)));
+    s = std::max<int64_t>(1, std::min<int64_t>({s, (int64_t)MAX_SHARDS, tiles}));
+    int64_t per = (tiles + s - 1) / s;                 /* tiles of a slice */
+    if (per * EXACT_ROW_ALIGN > INT32_MAX) per = (tiles + 1) / 2;   /* rows is an int32 */
+    return {(int32_t)((tiles + per - 1) / per), (int32_t)(per * EXACT_ROW_ALIGN)};
+}
+
+/* exact top-k into device buffers; the handle's lock is held and its device
+ * current. Returns once the output is complete. */
+static int exact_device_core(SptagAmdIndex* ix, const void* d_q, int32_t nq, int32_t k,
+                             int32_t* d_vids, float* d_dists)
+{
+    int ncu = 0;
+    HIP_OR_FAIL(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount,
+                                      ix->device), SPTAG_AMD_ERR_NOGPU);
+    const char* e = getenv("SPTAG_AMD_EXACT_SLICES");
+    const ExactCut cut = plan_exact(ix->n, nq, k, ncu, e ? atoi(e) : 0);
+    int32_t* lv = d_vids;       /* one slice: its lists are the answer */
+    float* ld = d_dists;
+    if (cut.slices > 1) {
+        const size_t bytes = (size_t)cut.slices * nq * k * 4;
+        HIP_OR_FAIL(ix->d_exact_v.ensure(bytes), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(ix->d_exact_d.ensure(bytes), SPTAG_AMD_ERR_OOM);
+        lv = ix->d_exact_v.as<int32_t>();
+        ld = ix->d_exact_d.as<float>();
+    }
+    int err = launch_exact(ix->vt, ix->dm, ix->dev(), d_q, nq, k, cut.slices, cut.rows,
+                           lv, ld);
+    if (err == 0 && cut.slices > 1)
+        err = launch_merge_topk(lv, ld, MergeBases{}, cut.slices, nq, k, k, d_vids,
+                                d_dists);
+    if (err != 0) {
+        fprintf(stderr, "sptag_amd: exact search launch failed %d\n", err);
+        return SPTAG_AMD_ERR_INTERNAL;
+    }
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+static int check_exact_args(SptagAmdIndex* ix, const void* q, int32_t nq, int32_t k,
+                            const void* out_vids, const void* out_dists)
+{
+    if (!ix || !q || nq <= 0 || k <= 0 || k > MAX_K || !out_vids || !out_dists)
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available() || !ix->d_vectors) return SPTAG_AMD_ERR_NOGPU;
+    return SPTAG_AMD_OK;
+}
+
+int sptag_amd_exact_search_device(SptagAmdIndex* ix, const void* d_queries, int32_t nq,
+                                  int32_t k, int32_t* d_out_vids, float* d_out_dists)
+{
+    int rc = check_exact_args(ix, d_queries, nq, k, d_out_vids, d_out_dists);
+    if (rc != SPTAG_AMD_OK) return rc;
+    std::lock_guard<std::mutex> g(ix->lock);
+    HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
+    return exact_device_core(ix, d_queries, nq, k, d_out_vids, d_out_dists);
+}
+
+int sptag_amd_exact_search(SptagAmdIndex* ix, const void* queries, int32_t nq, int32_t k,
+                           int32_t* out_vids, float* out_dists)
+{
+    int rc = check_exact_args(ix, queries, nq, k, out_vids, out_dists);
+    if (rc != SPTAG_AMD_OK) return rc;
+    std::lock_guard<std::mutex> g(ix->lock);
+    HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
+
+    const size_t n = (size_t)nq * k;
+    DevBuf d_q;
+    TopkOut out;
+    if ((rc = dev_upload(d_q, queries, (size_t)nq * ix->dim * ix->esz())) != SPTAG_AMD_OK)
+        return rc;
+    if ((rc = out.ensure(n)) != SPTAG_AMD_OK) return rc;
+    rc = exact_device_core(ix, d_q.as(), nq, k, out.vids(), out.dists());
+    return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, n);
+}
+
 /* Host-side distance restatements for the add path's edge arithmetic
  * (RebuildNeighbors / InsertNeighbors recompute pair distances on the
  * host, as the reference does on CPU): same rounding contracts as the
@@ -1532,8 +1623,12 @@ int sptag_amd_shards_search_batch(SptagAmdShards* set, const void* queries, int3
     return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, n);
 }
 
-int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries, int32_t nq,
-                           int32_t k, int32_t* out_vids, float* out_dists)
+/* per-shard exact top-k (`one`: sptag_amd_truth or sptag_amd_exact_search)
+ * gathered on the host, then the set's merge */
+static int shards_topk_via(SptagAmdShards* set, const void* queries, int32_t nq, int32_t k,
+                        int32_t* out_vids, float* out_dists,
+                        int (*one)(SptagAmdIndex*, const void*, int32_t, int32_t, int32_t*,
+                                   float*))
 {
     int rc = check_shards_args(set, queries, nq, k);
     if (rc != SPTAG_AMD_OK) return rc;
@@ -1544,8 +1639,8 @@ int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries, int32_t nq,
     std::vector<float> hd((size_t)S * list);
     rc = for_each_group(set, [&](ShardGroup& g) -> int {
         for (int s : g.ids) {
-            int r = sptag_amd_truth(set->shards[s], queries, nq, k,
-                                    hv.data() + s * list, hd.data() + s * list);
+            int r = one(set->shards[s], queries, nq, k, hv.data() + s * list,
+                        hd.data() + s * list);
             if (r != SPTAG_AMD_OK) return r;
         }
         return SPTAG_AMD_OK;
@@ -1553,6 +1648,19 @@ int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries, int32_t nq,
     if (rc != SPTAG_AMD_OK) return rc;
     return sptag_amd_merge_topk(set->groups[0].device, S, nq, k, k, hv.data(),
                                 hd.data(), set->bases.b, out_vids, out_dists);
+}
+
+int sptag_amd_shards_truth(SptagAmdShards* set, const void* queries, int32_t nq,
+                           int32_t k, int32_t* out_vids, float* out_dists)
+{
+    return shards_topk_via(set, queries, nq, k, out_vids, out_dists, sptag_amd_truth);
+}
+
+int sptag_amd_shards_exact_search(SptagAmdShards* set, const void* queries, int32_t nq,
+                                  int32_t k, int32_t* out_vids, float* out_dists)
+{
+    return shards_topk_via(set, queries, nq, k, out_vids, out_dists,
+                           sptag_amd_exact_search);
 }
 
 }  /* extern "C" */
