@@ -134,6 +134,43 @@ int sptag_amd_exact_search_device(SptagAmdIndex* idx, const void* d_queries,
                                   int32_t nq, int32_t k, int32_t* d_out_vids,
                                   float* d_out_dists);
 
+/* Grouped exact kNN: all-pairs top-k inside row groups (the index builder's
+ * leaf step). Group g is members[starts[g] : starts[g] + counts[g]], vector
+ * ids in any order; no id occurs twice and an id may be in no group. Row v
+ * of out_vids/out_dists ([n][k], n the handle's row count) receives the k
+ * smallest (dist, vid) over the OTHER members of v's group: ascending (dist,
+ * vid), distances exactly those of the search paths for the handle's value
+ * type and metric, vid = -1 at MaxDist as padding behind the real entries.
+ * Only v itself is left out, by id: another id with an identical vector is a
+ * neighbour at its distance. The row of an id that is in no group, or alone
+ * in its group, is all padding; every row is written. The delete set, the
+ * tree and the graph are not consulted (BKT and KDT handles alike): the
+ * caller decides what is a member. Any 1 <= k <= 1024 and any group size,
+ * up to one group of all n rows. Computed by the grouped tiles of exact.hip:
+ * a workgroup owns 32 members of a group as queries and streams the group.
+ * Returns SPTAG_AMD_ERR_PARAM, with the outputs untouched, for a null
+ * pointer, k outside [1, 1024], ngroups < 1, a negative start or count, a
+ * group that ends past nmembers, two groups that overlap, a member outside
+ * [0, n) and an id that occurs twice in members. */
+int sptag_amd_group_knn(SptagAmdIndex* idx, const int32_t* members, int32_t nmembers,
+                        const int32_t* starts, const int32_t* counts, int32_t ngroups,
+                        int32_t k, int32_t* out_vids, float* out_dists);
+/* The same without a handle: d_vectors ([n][dim] of valuetype), d_members
+ * and the outputs are HIP device buffers on `device`; starts and counts stay
+ * host arrays (one entry per group). It checks what the host can see (the
+ * pointers, k, the ranges of starts/counts, value type, metric, 1 <= dim <=
+ * 4096, the int8 dim guard of the create calls) and returns
+ * SPTAG_AMD_ERR_PARAM for those. That every member is inside [0, n) and
+ * occurs once is the CALLER'S to guarantee: a member outside [0, n) makes
+ * the kernels read outside d_vectors. Runs on the default stream and returns
+ * after a device synchronise, as sptag_amd_exact_search_device does. */
+int sptag_amd_group_knn_device(int device, const void* d_vectors, int valuetype,
+                               int distmethod, int32_t n, int32_t dim,
+                               const int32_t* d_members, int32_t nmembers,
+                               const int32_t* starts, const int32_t* counts,
+                               int32_t ngroups, int32_t k, int32_t* d_out_vids,
+                               float* d_out_dists);
+
 /* Iterative (streaming) search — mirrors the reference's ResultIterator /
  * SearchIndexIterativeNext protocol (inc/Core/VectorIndex.h:43-49,
  * src/Core/ResultIterator.cpp) over a BATCH of nq per-query iterators whose

@@ -15,8 +15,8 @@ import os
 
 import numpy as np
 
-__all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "MetadataSet",
-           "load_library", "gpu_available", "SptagAmdError"]
+__all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "group_knn_device",
+           "MetadataSet", "load_library", "gpu_available", "SptagAmdError"]
 
 _LIB = None
 _LIBPATH = os.environ.get(
@@ -76,6 +76,17 @@ def load_library():
     lib.sptag_amd_exact_search.argtypes = lib.sptag_amd_truth.argtypes
     lib.sptag_amd_exact_search_device.restype = ctypes.c_int
     lib.sptag_amd_exact_search_device.argtypes = lib.sptag_amd_truth.argtypes
+    lib.sptag_amd_group_knn.restype = ctypes.c_int
+    lib.sptag_amd_group_knn.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p]
+    lib.sptag_amd_group_knn_device.restype = ctypes.c_int
+    lib.sptag_amd_group_knn_device.argtypes = [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_void_p]
     lib.sptag_amd_save_index.restype = ctypes.c_int
     lib.sptag_amd_save_index.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     for f in ["num_vectors", "dim", "valuetype", "distmethod", "degree",
@@ -344,6 +355,28 @@ class AnnIndex:
         if rc != 0:
             raise SptagAmdError(rc, "exact_search_device")
 
+    def GroupKnn(self, members, starts, counts, k):
+        """Exact kNN inside row groups: group g is members[starts[g] :
+        starts[g] + counts[g]] (vector ids, any order, none twice). Returns
+        (vids int32 [n,k], dists f32 [n,k]) indexed by vector id: the k
+        nearest OTHER members of the id's group, ascending (dist, vid),
+        vid=-1 padding; all padding for an id in no group."""
+        members = np.ascontiguousarray(members, dtype=np.int32)
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if starts.shape != counts.shape or starts.ndim != 1:
+            raise ValueError("starts and counts must be 1-d and of one length")
+        n = self.n
+        vids = np.empty((n, k), dtype=np.int32)
+        dists = np.empty((n, k), dtype=np.float32)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = self._lib.sptag_amd_group_knn(
+            self._h, p(members), members.size, p(starts), p(counts),
+            starts.size, k, p(vids), p(dists))
+        if rc != 0:
+            raise SptagAmdError(rc, "group_knn")
+        return vids, dists
+
     def Add(self, vectors, normalized=False):
         """Online add (reference AddIndex semantics below the tree-rebuild
         threshold); runs GPU refine searches per added vector."""
@@ -394,6 +427,29 @@ class AnnIndex:
         rc = self._lib.sptag_amd_save_index(self._h, str(folder).encode())
         if rc != 0:
             raise SptagAmdError(rc, "save_index")
+
+
+def group_knn_device(d_vectors_ptr, valuetype, distmethod, n, dim,
+                     d_members_ptr, nmembers, starts, counts, k, d_vids_ptr,
+                     d_dists_ptr, device=0):
+    """AnnIndex.GroupKnn without a handle, on HIP device addresses (e.g. torch
+    tensors' .data_ptr()): vectors [n, dim] of `valuetype`, int32 members
+    [nmembers], outputs int32 / float32 [n, k]. starts and counts are host
+    arrays. The caller guarantees that every member is inside [0, n) and
+    occurs once."""
+    starts = np.ascontiguousarray(starts, dtype=np.int32)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    if starts.shape != counts.shape or starts.ndim != 1:
+        raise ValueError("starts and counts must be 1-d and of one length")
+    dm = {"L2": DM_L2, "Cosine": DM_COSINE}.get(distmethod, distmethod)
+    rc = load_library().sptag_amd_group_knn_device(
+        device, ctypes.c_void_p(d_vectors_ptr), valuetype, dm, n, dim,
+        ctypes.c_void_p(d_members_ptr), nmembers,
+        starts.ctypes.data_as(ctypes.c_void_p),
+        counts.ctypes.data_as(ctypes.c_void_p), starts.size, k,
+        ctypes.c_void_p(d_vids_ptr), ctypes.c_void_p(d_dists_ptr))
+    if rc != 0:
+        raise SptagAmdError(rc, "group_knn_device")
 
 
 def merge_topk(vids, dists, vid_base, k, device=0):

@@ -11,7 +11,8 @@ Mirrors the reference build SEMANTICS (citations to /root/reference/AnnService):
     REFERENCE is judged by search recall/QPS on the produced index; an edit
     of this file is judged on bytes against its parent.
   - KNN graph: TP-tree partitions, exact KNN inside each leaf, candidates
-    merged over trees (NeighborhoodGraph.h:301-360);
+    merged over trees (NeighborhoodGraph.h:301-360); the leaf step is torch
+    by default and the grouped-kNN HIP kernels with leaf_knn="hip";
   - RNG prune: candidates ascending by distance, accept c iff for every
     already-accepted b: RNGFactor*dist(b,c) >= dist(q,c), up to degree, pad
     -1 (RelativeNeighborhoodGraph.h:18-35 RebuildNeighbors).
@@ -425,6 +426,36 @@ def _leaf_knn(xf, perm, starts, counts, kper, chunk_rows=1_000_000):
     return ids, dst
 
 
+def _leaf_knn_hip(xf, perm, starts, counts, kper):
+    """_leaf_knn by the grouped-kNN HIP kernels (sptag_amd.group_knn_device):
+    the same shapes and padding, with the search path's f32 L2 distances
+    in place of the |a|^2 + |b|^2 - 2ab identity, ties by id, and no padded
+    [B, m, m] tensor."""
+    if xf.device.type != "cuda":
+        raise RuntimeError('leaf_knn="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
+    from . import group_knn_device, VT_FLOAT, DM_L2
+    n, d = xf.shape
+    xf = xf.contiguous()
+    k = min(kper, max(1, int(counts.max()) - 1))
+    members = perm.to(torch.int32).contiguous()
+    ids = torch.empty((n, k), dtype=torch.int32, device=xf.device)
+    dst = torch.empty((n, k), dtype=torch.float32, device=xf.device)
+    torch.cuda.synchronize(xf.device)     # the library runs on the default stream
+    group_knn_device(xf.data_ptr(), VT_FLOAT, DM_L2, n, d, members.data_ptr(),
+                     members.numel(), starts.cpu().numpy(), counts.cpu().numpy(),
+                     k, ids.data_ptr(), dst.data_ptr(),
+                     device=xf.device.index or 0)
+    dst.masked_fill_(ids < 0, float("inf"))
+    if k < kper:
+        ids = torch.nn.functional.pad(ids, (0, kper - k), value=-1)
+        dst = torch.nn.functional.pad(dst, (0, kper - k), value=float("inf"))
+    return ids, dst
+
+
+_LEAF_KNN = {"torch": _leaf_knn, "hip": _leaf_knn_hip}
+
+
 def _merge_candidates(ids_a, dst_a, ids_b, dst_b, cand, self_ids,
                       row_chunk=None, out=None):
     """Merge two candidate lists per point: dedupe ids, keep `cand` nearest,
@@ -570,10 +601,14 @@ def _rng_prune(xf, cid, cdd, degree, rng_factor, fill_pruned=False):
 
 def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
                     rng_factor=1.0, seed=2016, device=None, point_chunk=None,
-                    verbose=False):
+                    verbose=False, leaf_knn="torch"):
     """Returns (graph, cand_ids, cand_dst), tensors on the device: graph
     int32 [n, degree] (RNG-pruned, ascending, -1 padded) and the [n, cand]
-    candidate pools it was pruned from, which the refine steps grow."""
+    candidate pools it was pruned from, which the refine steps grow.
+    leaf_knn: "torch" (padded GEMM + topk) or "hip" (the grouped-kNN
+    kernels; GPU only) for the exact KNN inside the TP-tree leaves."""
+    if leaf_knn not in _LEAF_KNN:
+        raise ValueError(f'leaf_knn must be "torch" or "hip", got {leaf_knn!r}')
     device, xf, gen = _prologue(vectors, device, seed + 77)
     n = xf.shape[0]
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
@@ -582,7 +617,7 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
     ids = dst = None
     for t in range(ntrees):
         perm, starts, counts = _tpt_leaves(xf, tpt_leaf, gen)
-        tids, tdst = _leaf_knn(xf, perm, starts, counts, kper)
+        tids, tdst = _LEAF_KNN[leaf_knn](xf, perm, starts, counts, kper)
         if ids is None:
             ids, dst = _merge_candidates(tids, tdst, tids[:, :0], tdst[:, :0],
                                          cand, self_ids)
@@ -772,7 +807,7 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
                        refine_rounds=0, search_refine_rounds=0, kdt_trees=1,
                        srefine_k=512, srefine_mc=8192, fill_pruned=False,
                        seed=2016, device=None, normalized=False,
-                       verbose=False):
+                       verbose=False, leaf_knn="torch"):
     """Full build: returns dict(vectors, tree_start, tree_nodes, graph) ready
     for AnnIndex.FromArrays (vectors already cosine-normalized when needed,
     as the reference stores them on disk)."""
@@ -789,7 +824,7 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
         print(f"  {algo} tree: {len(tree_nodes)} nodes")
     graph, cids, cdst = build_rng_graph(
         vectors, degree=degree, ntrees=ntrees, tpt_leaf=tpt_leaf, cand=cand,
-        seed=seed, device=device, verbose=verbose)
+        seed=seed, device=device, verbose=verbose, leaf_knn=leaf_knn)
     if refine_rounds > 0:
         graph, cids, cdst = refine_graph(
             vectors, graph, cids, cdst, degree=degree, cand=cand,

@@ -203,6 +203,19 @@ int launch_exact(int valuetype, int distmethod, const DevIndex& di,
                  const void* queries, int32_t nq, int32_t k, int32_t nslices,
                  int32_t rows_per_slice, int32_t* lists_v, float* lists_d);
 
+/* Grouped kNN (exact.hip): group g is members[start : start + count], vids of
+ * `vectors` ([n][dim]) in any order, no vid twice; row v of out_v/out_d
+ * ([n][k]) receives the k smallest (dist, vid) over the other members of v's
+ * group, padded with vid = -1 at MaxDist, and the row of a vid in no group
+ * is all padding. A workgroup owns one GroupTile: the EXACT_QT members of a
+ * group from q0 on as queries, q0 a multiple of EXACT_QT below count. The
+ * tiles cover every member of every group once. All pointers are device
+ * memory; every member is inside [0, n). */
+struct GroupTile { int32_t start, count, q0; };
+int launch_group_knn(int valuetype, int distmethod, const void* vectors, int32_t n,
+                     int32_t dim, const int32_t* members, const GroupTile* tiles,
+                     int32_t ntiles, int32_t k, int32_t* out_v, float* out_d);
+
 /* heap probe (tests/test_gpu_heap_ops.py): a script of nops heap operations
  * (ops[i] != 0: insert {nodes[i], dists[i]}; 0: pop) on a heap of capacity
  * `cap` whose entries [0..lsplit] sit in LDS (lsplit 0: none), run once with

@@ -35,6 +35,10 @@
  *   in the [S][nq][k] buffer itself, in global memory: they are touched only
  *   by merges, which are rare after the first tiles, and so one path serves
  *   every k <= MAX_K.
+ *
+ * Grouped kNN (all pairs inside row groups, the index builder's leaf step)
+ * runs on the same tiles and the same selection, with gathered loads and
+ * the lists in the output rows: see its section below.
  */
 #include <hip/hip_runtime.h>
 
@@ -64,11 +68,18 @@ struct XSel {
     float* thr;      /* LDS [XQT] */
     int* cnt;        /* LDS [XQT]; may run past XCB, entries past it were not stored */
     XCand* cand;     /* LDS [XQT][XCB] */
-    int32_t* lv;     /* this (slice, query tile)'s lists, query ql at ql*k */
+    int32_t* lv;     /* the lists; query ql's is row qrow[ql] of k entries */
     float* ld;
     int k;
     int nql;         /* queries of the tile that exist */
+    const int32_t* qrow;   /* LDS [XQT]; null: row ql (exact search, whose lv/ld
+                              start at its (slice, query tile)) */
 };
+
+DEV size_t sel_list_at(const XSel& s, int ql)
+{
+    return (size_t)(s.qrow ? s.qrow[ql] : ql) * s.k;
+}
 
 /* (da, va) ordered before (db, vb); vids are distinct, so this is total */
 DEV bool key_before(float da, int32_t va, float db, int32_t vb)
@@ -134,8 +145,8 @@ DEV void flush_cands(const XSel& s, int level)
     for (int ql = wave; ql < s.nql; ql += XWAVES) {
         const int n = min(__builtin_amdgcn_readfirstlane(s.cnt[ql]), (int)XCB);
         if (n < level || n == 0) continue;
-        int32_t* lv = s.lv + (size_t)ql * s.k;
-        float* ld = s.ld + (size_t)ql * s.k;
+        int32_t* lv = s.lv + sel_list_at(s, ql);
+        float* ld = s.ld + sel_list_at(s, ql);
         merge_cands(lv, ld, s.k, s.cand + ql * XCB, n);
         const float kth = ld[s.k - 1];
         if (lane == 0) { s.cnt[ql] = 0; s.thr[ql] = kth; }
@@ -147,11 +158,13 @@ DEV void sel_init(const XSel& s)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (threadIdx.x < XQT) { s.thr[threadIdx.x] = MAXDIST; s.cnt[threadIdx.x] = 0; }
-    for (int ql = wave; ql < s.nql; ql += XWAVES)
+    for (int ql = wave; ql < s.nql; ql += XWAVES) {
+        const size_t at = sel_list_at(s, ql);
         for (int i = lane; i < s.k; i += 64) {
-            s.lv[(size_t)ql * s.k + i] = -1;
-            s.ld[(size_t)ql * s.k + i] = MAXDIST;
+            s.lv[at + i] = -1;
+            s.ld[at + i] = MAXDIST;
         }
+    }
     __threadfence();
     __syncthreads();
 }
@@ -203,6 +216,7 @@ DEV XSel make_sel(unsigned char* lds, uint32_t thr, uint32_t cnt, uint32_t cand,
     s.ld = lists_d + at;
     s.k = k;
     s.nql = min((int)XQT, nq - q0);
+    s.qrow = nullptr;
     return s;
 }
 
@@ -259,6 +273,27 @@ DEV float dpp(float v)
 enum { DPP_ROW_SHL8 = 0x108, DPP_ROW_SHL4 = 0x104,     /* lane g reads lane g + n */
        DPP_QUAD0 = 0x00, DPP_QUAD1 = 0x55, DPP_QUAD2 = 0xaa, DPP_QUAD3 = 0xff };
 
+/* The gathered form of f32_slab_load below (grouped kNN): columns
+ * k0 + 4*(tid%16) .. +3 of the row of d floats at `row`, zero past d and for
+ * a null row. vec: the row and the columns are 16-byte aligned. */
+DEV float4 f32_cols_load(const float* __restrict__ row, int d, int k0, bool vec)
+{
+    const int c = k0 + (threadIdx.x & 15) * 4;
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (row && c < d) {
+        const float* p = row + c;
+        if (vec) {
+            v = *(const float4*)p;
+        } else {
+            v.x = p[0];
+            if (c + 1 < d) v.y = p[1];
+            if (c + 2 < d) v.z = p[2];
+            if (c + 3 < d) v.w = p[3];
+        }
+    }
+    return v;
+}
+
 /* The block's threads cover 16 rows x FKS columns with four columns each:
  * this thread's are row r = r16 + tid/16, columns k0 + 4*(tid%16) .. +3 of
  * `base`'s rows (row pitch d), zero outside nrows x d. vec: rows and columns
@@ -285,6 +320,83 @@ DEV float4 f32_slab_load(const float* __restrict__ base, int nrows, int d, int k
 DEV void f32_slab_store(float* buf, int stride, float4 v, int r16 = 0)
 {
     *(float4*)(buf + (r16 + (threadIdx.x >> 4)) * stride + (threadIdx.x & 15) * 4) = v;
+}
+
+/* f32_slab_math and f32_fold are the grouped-kNN kernel's statement of the
+ * slab loop and the fold that exact_f32_kernel spells out in its body. With
+ * both kernels calling them, and f32_slab_load going through f32_cols_load,
+ * the compiler scheduled exact_f32_kernel differently and exact search came
+ * out 6% slower (profiles/group_knn.txt), so that kernel keeps its text; the
+ * tests pin both to the same reference bits.
+ *
+ * One slab of a group's micro-tile: the whole 16-column chunks of slab `slab`
+ * (columns slab*FKS ..) go into lane g's accumulators, cleared at slab 0.
+ * qb: this group's query gq of the slab (query gq + 4*i at + 4*i*qstride);
+ * rb: this wave's first row of the slab (row j at + j*FKS). */
+template <int DM>
+DEV void f32_slab_math(float (&acc)[FMQ][FMR], const float* qb, const float* rb, int qstride,
+                       int slab, int d, int g)
+{
+    if (slab == 0) {
+#pragma unroll
+        for (int i = 0; i < FMQ; i++)
+#pragma unroll
+            for (int j = 0; j < FMR; j++) acc[i][j] = 0.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < FKS / 16; c++) {
+        if (slab * FKS + c * 16 + 16 > d) break;
+        float x[FMQ], y[FMR];
+#pragma unroll
+        for (int i = 0; i < FMQ; i++) x[i] = qb[4 * i * qstride + c * 16 + g];
+#pragma unroll
+        for (int j = 0; j < FMR; j++) y[j] = rb[j * FKS + c * 16 + g];
+#pragma unroll
+        for (int i = 0; i < FMQ; i++)
+#pragma unroll
+            for (int j = 0; j < FMR; j++) acc[i][j] = xstep<DM>(x[i], y[j], acc[i][j]);
+    }
+}
+
+/* After the last slab: the reference's folds and tails. dist[i] on lane
+ * g < FMR is the distance of query gq + 4*i to row g of the wave's four. */
+template <int DM>
+DEV void f32_fold(const float (&acc)[FMQ][FMR], const float* qb, const float* rb, int qstride,
+                  int slab, int d, int g, float (&dist)[FMQ])
+{
+    const int nd16 = d & ~15, nd8 = d & ~7, nd4 = d & ~3;
+    /* the tails' columns sit in this slab, from tc on */
+    const int tc = nd16 - slab * FKS;
+    float x8[FMQ], x4[FMQ], y8[FMR], y4[FMR];
+#pragma unroll
+    for (int i = 0; i < FMQ; i++) {
+        x8[i] = (nd8 > nd16 && g < 8) ? qb[4 * i * qstride + tc + g] : 0.0f;
+        x4[i] = (nd4 > nd8 && g < 4) ? qb[4 * i * qstride + tc + (nd8 - nd16) + g] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < FMR; j++) {
+        y8[j] = (nd8 > nd16 && g < 8) ? rb[j * FKS + tc + g] : 0.0f;
+        y4[j] = (nd4 > nd8 && g < 4) ? rb[j * FKS + tc + (nd8 - nd16) + g] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < FMQ; i++) {
+        float mine = 0.0f;
+#pragma unroll
+        for (int j = 0; j < FMR; j++) {
+            float a = acc[i][j];
+            a = a + dpp<DPP_ROW_SHL8>(a);               /* a8[g] on g < 8 */
+            if (nd8 > nd16) a = xstep<DM>(x8[i], y8[j], a);
+            a = a + dpp<DPP_ROW_SHL4>(a);               /* a4[g] on g < 4 */
+            if (nd4 > nd8) a = xstep<DM>(x4[i], y4[j], a);
+            const float s = ((dpp<DPP_QUAD0>(a) + dpp<DPP_QUAD1>(a)) +
+                             dpp<DPP_QUAD2>(a)) + dpp<DPP_QUAD3>(a);
+            mine = (j == 0 || g == j) ? s : mine;
+        }
+        for (int c = nd4; c < d; c++)
+            mine = xstep<DM>(qb[4 * i * qstride + (c - slab * FKS)],
+                             rb[(g & 3) * FKS + (c - slab * FKS)], mine);
+        dist[i] = (DM == DM_L2) ? mine : 1.0f - mine;
+    }
 }
 
 /* QRES: the whole query tile stays in LDS; otherwise (large dims) its slab
@@ -494,6 +606,31 @@ DEV v4i i8_operand(const uint32_t* row, int kb, int W)
     return v;
 }
 
+/* A wave's 32 queries x 32 rows of dots: arow/brow are this lane's query and
+ * row (lane % 32) in LDS, h = lane / 32 the half of each 32-byte K step it
+ * feeds. bb (L2): the row's self-dot. */
+template <int DM>
+DEV void i8_tile_dots(const uint32_t* arow, const uint32_t* brow, int W, int h, v16i& acc,
+                      int& bb)
+{
+    acc = v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bb = 0;
+    const int nks = (W + 7) >> 3;
+    for (int ks = 0; ks < nks; ks++) {
+        const int kb = ks * 8 + h * 4;
+        const v4i a = i8_operand(arow, kb, W);
+        const v4i b = i8_operand(brow, kb, W);
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+        if (DM == DM_L2) {
+            bb = __builtin_amdgcn_sdot4(b.x, b.x, bb, false);
+            bb = __builtin_amdgcn_sdot4(b.y, b.y, bb, false);
+            bb = __builtin_amdgcn_sdot4(b.z, b.z, bb, false);
+            bb = __builtin_amdgcn_sdot4(b.w, b.w, bb, false);
+        }
+    }
+    if (DM == DM_L2) bb += __shfl_xor(bb, 32);      /* both halves of the row's bytes */
+}
+
 template <int DM>
 __global__ __launch_bounds__(XTHREADS, 2)
 void exact_i8_kernel(DevIndex di, const int8_t* __restrict__ queries, int32_t nq, int32_t k,
@@ -590,26 +727,13 @@ void exact_i8_kernel(DevIndex di, const int8_t* __restrict__ queries, int32_t nq
     const int h = lane >> 5, col = lane & 31;
     const uint32_t* arow = qlds + col * WL;
     const uint32_t* brow = rlds + (wave * 32 + col) * WL;
-    const int nks = (d + 31) >> 5;
     for (int t = 0; t < ntile; t++) {
         const int tr0 = r0 + t * IRT;
         if (t + 1 < ntile) stage_load(tr0 + IRT);   /* in flight while this tile computes */
 
-        v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        int bb = 0;
-        for (int ks = 0; ks < nks; ks++) {
-            const int kb = ks * 8 + h * 4;
-            const v4i a = i8_operand(arow, kb, W);
-            const v4i b = i8_operand(brow, kb, W);
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
-            if (DM == DM_L2) {
-                bb = __builtin_amdgcn_sdot4(b.x, b.x, bb, false);
-                bb = __builtin_amdgcn_sdot4(b.y, b.y, bb, false);
-                bb = __builtin_amdgcn_sdot4(b.z, b.z, bb, false);
-                bb = __builtin_amdgcn_sdot4(b.w, b.w, bb, false);
-            }
-        }
-        if (DM == DM_L2) bb += __shfl_xor(bb, 32);      /* both halves of the row's bytes */
+        v16i acc;
+        int bb;
+        i8_tile_dots<DM>(arow, brow, W, h, acc, bb);
 
         /* acc[r] is query 8*(r/4) + 4*h + r%4 against row `col` of the wave's 32 */
         uint32_t pend = 0;
@@ -635,7 +759,335 @@ void exact_i8_kernel(DevIndex di, const int8_t* __restrict__ queries, int32_t nq
 }
 
 /* ------------------------------------------------------------------ *
- * launcher
+ * grouped kNN: all pairs inside row groups
+ * ------------------------------------------------------------------ *
+ * Group g is members[start : start + count], vids in any order; the answer
+ * of a member is its k nearest other members, in row `vid` of out[n][k]. A
+ * workgroup owns one GroupTile: XQT consecutive members of one group as its
+ * queries, against which it streams all members of the group as rows, with
+ * the tiles and the math of the exact kernels above. What differs:
+ *
+ *   gather  Queries and rows are vectors[members[..]]: every row of a tile
+ *           has a base of its own. The ids of a row tile are read one tile
+ *           ahead of its vectors (a register for f32, whose loader thread
+ *           needs one id; a double-buffered LDS array for int8, whose
+ *           thread touches several rows), so the vector loads of the next
+ *           tile leave before the current tile's math, as in exact search,
+ *           and never wait for an id. Loads are 16 bytes where the row pitch
+ *           and the base allow it, else dwords, else (int8 pitches that are
+ *           no multiple of 4) bytes packed at the LDS store.
+ *   lists   A query's list is its own output row (XSel::qrow = the query
+ *           vids): no slices, no merge kernel. group_fill_kernel pads the
+ *           whole output first, for the vids that are in no group.
+ *   admit   Rows arrive in member order, not vid order, so a row enters with
+ *           dist <= thr: keys are distinct, a row whose key is above the
+ *           k-th falls out in the merge, which ranks by (dist, vid).
+ *   self    The pair (v, v) is skipped by vid; another vid with the same
+ *           vector is a neighbour at its distance. */
+
+struct GrpLds { uint32_t qvid, mids, total; };
+
+/* behind the exact kernel's regions: the query vids and 2 x rt row-tile ids */
+static inline __host__ __device__ GrpLds grp_lds(uint32_t base, int rt)
+{
+    GrpLds l;
+    l.qvid = base;
+    l.mids = l.qvid + XQT * 4;
+    l.total = l.mids + 2 * rt * 4;
+    return l;
+}
+
+__global__ __launch_bounds__(256)
+void group_fill_kernel(int32_t* out_v, float* out_d, size_t total)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * 256) {
+        out_v[i] = -1;
+        out_d[i] = MAXDIST;
+    }
+}
+
+/* the tile's query vids into LDS (-1 past the group's end); returns how many
+ * exist. Ends with a barrier. */
+DEV int group_queries(const GroupTile& T, const int32_t* __restrict__ members, int32_t* qvid)
+{
+    const int nql = min((int)XQT, T.count - T.q0);
+    if (threadIdx.x < XQT)
+        qvid[threadIdx.x] = (int)threadIdx.x < nql ? members[T.start + T.q0 + threadIdx.x] : -1;
+    __syncthreads();
+    return nql;
+}
+
+template <int DM, bool QRES>
+__global__ __launch_bounds__(XTHREADS, 2)
+void group_f32_kernel(const float* __restrict__ vectors, int d,
+                      const int32_t* __restrict__ members,
+                      const GroupTile* __restrict__ tiles, int32_t k, int32_t* out_v,
+                      float* out_d)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const F32Lds L = f32_lds(d);
+    const GrpLds G = grp_lds(L.total, FRT);
+    float* qlds = (float*)(xlds + L.q);
+    float* rlds = (float*)(xlds + L.rows);
+    int32_t* qvid = (int32_t*)(xlds + G.qvid);
+    int32_t* mids = (int32_t*)(xlds + G.mids);     /* [2][FRT], by tile parity */
+    const int tid = threadIdx.x;
+    const int g = tid & 15, gq = (tid >> 4) & 3, gr = tid >> 6, lr = tid >> 4;
+    const GroupTile T = tiles[blockIdx.x];
+    const int32_t* mem = members + T.start;
+    const int nql = group_queries(T, members, qvid);
+    const XSel sel = {(float*)(xlds + L.thr), (int*)(xlds + L.cnt), (XCand*)(xlds + L.cand),
+                      out_v, out_d, k, nql, qvid};
+    const bool vec = (d & 3) == 0 && ((uintptr_t)vectors & 15) == 0;
+    const int qstride = QRES ? f32_qstride(d) : FQSS;
+
+    /* this thread's slab columns of the vector `id` */
+    auto cols = [&](int32_t id, int k0) {
+        return f32_cols_load(id >= 0 ? vectors + (size_t)id * d : nullptr, d, k0, vec);
+    };
+    /* the member this thread loads for row tile t: row lr of it */
+    auto row_id = [&](int t) {
+        const int ri = t * FRT + lr;
+        return ri < T.count ? mem[ri] : -1;
+    };
+
+    int32_t qid0 = -1, qid1 = -1;       /* streamed query rows lr and 16 + lr */
+    if constexpr (QRES) {
+        for (int i = tid; i < XQT * qstride; i += XTHREADS) {
+            const int r = i / qstride, c = i - r * qstride;
+            qlds[i] = (r < nql && c < d) ? vectors[(size_t)qvid[r] * d + c] : 0.0f;
+        }
+    } else {
+        qid0 = qvid[lr];
+        qid1 = qvid[16 + lr];
+    }
+    sel_init(sel);
+
+    const int nslab = (d + FKS - 1) / FKS;
+    const int ntile = (T.count + FRT - 1) / FRT;
+    const int nstep = ntile * nslab;            /* >= 1: a group is not empty */
+
+    float acc[FMQ][FMR];
+    int32_t idc = row_id(0), idn = row_id(1);   /* of the tile being loaded, and the next */
+    float4 pr = cols(idc, 0), pq0 = pr, pq1 = pr;
+    f32_slab_store(rlds, FKS, pr);
+    if (g == 0) mids[lr] = idc;
+    if constexpr (!QRES) {
+        pq0 = cols(qid0, 0);
+        pq1 = cols(qid1, 0);
+        f32_slab_store(qlds, FQSS, pq0, 0);
+        f32_slab_store(qlds, FQSS, pq1, 16);
+    }
+    __syncthreads();
+
+    int tile = 0, slab = 0;
+    for (int st = 0; st < nstep; st++) {
+        int ntl = tile, nsl = slab + 1;
+        if (nsl == nslab) { nsl = 0; ntl++; }
+        const bool more = st + 1 < nstep;
+        if (more) {     /* in flight while this slab computes */
+            if (ntl != tile) {
+                idc = idn;
+                idn = row_id(ntl + 1);
+            }
+            pr = cols(idc, nsl * FKS);
+            if constexpr (!QRES) {
+                pq0 = cols(qid0, nsl * FKS);
+                pq1 = cols(qid1, nsl * FKS);
+            }
+        }
+        const float* rb = rlds + (st & 1) * (FRT * FKS) + (gr * FMR) * FKS;
+        const float* qb = (QRES ? qlds + slab * FKS : qlds + (st & 1) * (XQT * FQSS)) +
+                          gq * qstride;
+        f32_slab_math<DM>(acc, qb, rb, qstride, slab, d, g);
+
+        if (slab == nslab - 1) {
+            float dist[FMQ];
+            int ql[FMQ];
+            int32_t vid[FMQ];
+            uint32_t pend = 0;
+            const int32_t myvid = mids[(tile & 1) * FRT + gr * FMR + (g & 3)];
+            f32_fold<DM>(acc, qb, rb, qstride, slab, d, g, dist);
+#pragma unroll
+            for (int i = 0; i < FMQ; i++) {
+                ql[i] = gq + 4 * i;
+                vid[i] = myvid;
+                if (g < FMR && myvid >= 0 && ql[i] < nql && myvid != qvid[ql[i]] &&
+                    dist[i] <= sel.thr[ql[i]])
+                    pend |= 1u << i;
+            }
+            sel_append(sel, pend, dist, ql, vid);
+        }
+
+        if (more) {
+            f32_slab_store(rlds + ((st + 1) & 1) * (FRT * FKS), FKS, pr);
+            if (g == 0) mids[(ntl & 1) * FRT + lr] = idc;   /* read at ntl's last slab */
+            if constexpr (!QRES) {
+                f32_slab_store(qlds + ((st + 1) & 1) * (XQT * FQSS), FQSS, pq0, 0);
+                f32_slab_store(qlds + ((st + 1) & 1) * (XQT * FQSS), FQSS, pq1, 16);
+            }
+        }
+        __syncthreads();
+        tile = ntl;
+        slab = nsl;
+    }
+    flush_cands(sel, 1);
+}
+
+enum { GI_CPR_MAX = (I_MAX_W + 3) / 4,      /* 16-byte chunks of a row at the dim guard */
+       GI_NCH = (IRT * GI_CPR_MAX + XTHREADS - 1) / XTHREADS };  /* chunks per thread */
+
+template <int DM>
+__global__ __launch_bounds__(XTHREADS, 2)
+void group_i8_kernel(const int8_t* __restrict__ vectors, int d,
+                     const int32_t* __restrict__ members,
+                     const GroupTile* __restrict__ tiles, int32_t k, int32_t* out_v,
+                     float* out_d)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const I8Lds L = i8_lds(d);
+    const GrpLds G = grp_lds(L.total, IRT);
+    uint32_t* qlds = (uint32_t*)(xlds + L.q);
+    uint32_t* rlds = (uint32_t*)(xlds + L.rows);
+    int* aa = (int*)(xlds + L.aa);
+    int32_t* qvid = (int32_t*)(xlds + G.qvid);
+    int32_t* mids = (int32_t*)(xlds + G.mids);     /* [2][IRT], by tile parity */
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const GroupTile T = tiles[blockIdx.x];
+    const int32_t* mem = members + T.start;
+    const int nql = group_queries(T, members, qvid);
+    const XSel sel = {(float*)(xlds + L.thr), (int*)(xlds + L.cnt), (XCand*)(xlds + L.cand),
+                      out_v, out_d, k, nql, qvid};
+    const int W = (d + 3) >> 2, WL = W | 1, CPR = (W + 3) >> 2;
+    /* how a row may be read: 2 = 16 bytes, 1 = dwords, 0 = bytes */
+    const int wide = ((d & 15) == 0 && ((uintptr_t)vectors & 15) == 0) ? 2
+                   : ((d & 3) == 0 && ((uintptr_t)vectors & 3) == 0) ? 1 : 0;
+
+    for (int i = tid; i < XQT * W; i += XTHREADS) {
+        const int r = i / W, w = i - r * W;
+        uint32_t v = 0;
+        if (r < nql)
+            v = wide ? *(const uint32_t*)(vectors + (size_t)qvid[r] * d + 4 * w)
+                     : i8_pack_dword(vectors, qvid[r], w, d);
+        qlds[r * WL + w] = v;
+    }
+    /* the member of row tid of row tile t, -1 past the group's end */
+    auto tile_id = [&](int t) {
+        const int ri = t * IRT + tid;
+        return (tid < IRT && ri < T.count) ? mem[ri] : -1;
+    };
+    if (tid < IRT) {
+        mids[tid] = tile_id(0);
+        mids[IRT + tid] = tile_id(1);
+    }
+    int32_t idn = tile_id(2);           /* ids are read two tiles ahead of their use */
+    sel_init(sel);
+    if (tid < XQT) {        /* query self-dots, for L2 */
+        int s = 0;
+        for (int w = 0; w < W; w++) {
+            const int v = (int)qlds[tid * WL + w];
+            s = __builtin_amdgcn_sdot4(v, v, s, false);
+        }
+        aa[tid] = s;
+    }
+
+    /* chunk c of this thread is 16-byte chunk j of row r of the tile, with
+     * r * CPR + j = tid + c * XTHREADS; (r0, j0) is the first */
+    const int cr0 = tid / CPR, cj0 = tid - cr0 * CPR;
+    const int cdr = XTHREADS / CPR, cdj = XTHREADS - cdr * CPR;
+    uint4 pre[GI_NCH];
+    auto stage_load = [&](int t) {
+        if (!wide) return;
+        const int32_t* ids = mids + (t & 1) * IRT;
+        int r = cr0, j = cj0;
+#pragma unroll
+        for (int c = 0; c < GI_NCH; c++) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            const int32_t id = r < IRT ? ids[r] : -1;
+            if (id >= 0) {
+                const unsigned char* p = (const unsigned char*)vectors + (size_t)id * d + 16 * j;
+                if (wide == 2) {
+                    v = *(const uint4*)p;
+                } else {
+                    v.x = *(const uint32_t*)p;
+                    if (4 * j + 1 < W) v.y = *(const uint32_t*)(p + 4);
+                    if (4 * j + 2 < W) v.z = *(const uint32_t*)(p + 8);
+                    if (4 * j + 3 < W) v.w = *(const uint32_t*)(p + 12);
+                }
+            }
+            pre[c] = v;
+            r += cdr;
+            j += cdj;
+            if (j >= CPR) { j -= CPR; r++; }
+        }
+    };
+    auto stage_store = [&](int t) {
+        if (!wide) {
+            const int32_t* ids = mids + (t & 1) * IRT;
+            for (int i = tid; i < IRT * W; i += XTHREADS) {
+                const int r = i / W, w = i - r * W;
+                rlds[r * WL + w] = ids[r] >= 0 ? i8_pack_dword(vectors, ids[r], w, d) : 0u;
+            }
+            return;
+        }
+        int r = cr0, j = cj0;
+#pragma unroll
+        for (int c = 0; c < GI_NCH; c++) {
+            const uint32_t v[4] = {pre[c].x, pre[c].y, pre[c].z, pre[c].w};
+            if (r < IRT) {
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    if (4 * j + e < W) rlds[r * WL + 4 * j + e] = v[e];
+            }
+            r += cdr;
+            j += cdj;
+            if (j >= CPR) { j -= CPR; r++; }
+        }
+    };
+
+    const int ntile = (T.count + IRT - 1) / IRT;    /* >= 1 */
+    stage_load(0);          /* sel_init's barrier is behind the ids of tiles 0 and 1 */
+    stage_store(0);
+    __syncthreads();
+
+    const int h = lane >> 5, col = lane & 31;
+    const uint32_t* arow = qlds + col * WL;
+    const uint32_t* brow = rlds + (wave * 32 + col) * WL;
+    for (int t = 0; t < ntile; t++) {
+        if (t + 1 < ntile) stage_load(t + 1);   /* in flight while this tile computes */
+
+        v16i acc;
+        int bb;
+        i8_tile_dots<DM>(arow, brow, W, h, acc, bb);
+
+        uint32_t pend = 0;
+        float dist[16];
+        int ql[16];
+        int32_t vid[16];
+        const int32_t myvid = mids[(t & 1) * IRT + wave * 32 + col];
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            ql[r] = 8 * (r >> 2) + 4 * h + (r & 3);
+            vid[r] = myvid;
+            dist[r] = (DM == DM_L2) ? (float)(aa[ql[r]] - 2 * acc[r] + bb)
+                                    : (float)(16129 - acc[r]);
+            if (myvid >= 0 && ql[r] < nql && myvid != qvid[ql[r]] && dist[r] <= sel.thr[ql[r]])
+                pend |= 1u << r;
+        }
+        sel_append(sel, pend, dist, ql, vid);   /* ends with a barrier: the tile is free */
+
+        if (t + 1 < ntile) stage_store(t + 1);
+        /* tile t's ids are done with: tile t + 2's take their place */
+        if (tid < IRT) mids[(t & 1) * IRT + tid] = idn;
+        idn = tile_id(t + 3);
+        __syncthreads();
+    }
+    flush_cands(sel, 1);
+}
+
+/* ------------------------------------------------------------------ *
+ * launchers
  * ------------------------------------------------------------------ */
 
 int launch_exact(int vt, int dm, const DevIndex& di, const void* queries, int32_t nq,
@@ -663,6 +1115,38 @@ int launch_exact(int vt, int dm, const DevIndex& di, const void* queries, int32_
                            (const int8_t*)queries, nq, k, rows_per_slice, lists_v, lists_d);
     } else {
         return (int)hipErrorInvalidValue;
+    }
+    return (int)hipGetLastError();
+}
+
+int launch_group_knn(int vt, int dm, const void* vectors, int32_t n, int32_t dim,
+                     const int32_t* members, const GroupTile* tiles, int32_t ntiles,
+                     int32_t k, int32_t* out_v, float* out_d)
+{
+    if (n < 1 || dim < 1 || k < 1 || k > MAX_K || ntiles < 0 ||
+        (vt != VT_FLOAT && vt != VT_INT8) || (vt == VT_INT8 && dim > 4 * I_MAX_W))
+        return (int)hipErrorInvalidValue;
+    const size_t total = (size_t)n * k;
+    const size_t fblocks = (total + 255) / 256;
+    const unsigned fill = fblocks < 65536 ? (unsigned)fblocks : 65536u;   /* grid-stride */
+    hipLaunchKernelGGL(group_fill_kernel, dim3(fill), dim3(256), 0, nullptr, out_v, out_d,
+                       total);
+    if (ntiles == 0) return (int)hipGetLastError();
+    const dim3 grid(ntiles), block(XTHREADS);
+    if (vt == VT_FLOAT) {
+        const bool qres = f32_qstride(dim) <= FQRES_MAX;
+        auto kernel = dm == DM_L2 ? (qres ? group_f32_kernel<DM_L2, true>
+                                          : group_f32_kernel<DM_L2, false>)
+                                  : (qres ? group_f32_kernel<DM_COSINE, true>
+                                          : group_f32_kernel<DM_COSINE, false>);
+        hipLaunchKernelGGL(kernel, grid, block, grp_lds(f32_lds(dim).total, FRT).total,
+                           nullptr, (const float*)vectors, dim, members, tiles, k, out_v,
+                           out_d);
+    } else {
+        auto kernel = dm == DM_L2 ? group_i8_kernel<DM_L2> : group_i8_kernel<DM_COSINE>;
+        hipLaunchKernelGGL(kernel, grid, block, grp_lds(i8_lds(dim).total, IRT).total,
+                           nullptr, (const int8_t*)vectors, dim, members, tiles, k, out_v,
+                           out_d);
     }
     return (int)hipGetLastError();
 }

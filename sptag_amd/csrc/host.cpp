@@ -966,6 +966,101 @@ int sptag_amd_exact_search(SptagAmdIndex* ix, const void* queries, int32_t nq, i
     return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, n);
 }
 
+/* What both grouped-kNN entries can check from the host: k, and that every
+ * group is a range of the member list and no two ranges overlap. */
+static bool group_ranges_ok(int64_t nmembers, const int32_t* starts, const int32_t* counts,
+                            int32_t ngroups, int32_t k)
+{
+    if (!starts || !counts || ngroups < 1 || nmembers < 0 || k < 1 || k > MAX_K)
+        return false;
+    std::vector<int32_t> order;
+    for (int32_t g = 0; g < ngroups; g++) {
+        if (counts[g] < 0 || starts[g] < 0 || (int64_t)starts[g] + counts[g] > nmembers)
+            return false;
+        if (counts[g] > 0) order.push_back(g);
+    }
+    std::sort(order.begin(), order.end(),
+              [&](int32_t a, int32_t b) { return starts[a] < starts[b]; });
+    for (size_t i = 1; i < order.size(); i++)
+        if ((int64_t)starts[order[i - 1]] + counts[order[i - 1]] > starts[order[i]])
+            return false;
+    return true;
+}
+
+/* grouped kNN into device buffers, arguments checked; `device` is current.
+ * Returns once the output is complete. */
+static int group_knn_core(const void* d_vectors, int vt, int dm, int32_t n, int32_t dim,
+                          const int32_t* d_members, const int32_t* starts,
+                          const int32_t* counts, int32_t ngroups, int32_t k,
+                          int32_t* d_vids, float* d_dists)
+{
+    std::vector<GroupTile> tiles;
+    for (int32_t g = 0; g < ngroups; g++)
+        for (int32_t q0 = 0; q0 < counts[g]; q0 += EXACT_QT)
+            tiles.push_back({starts[g], counts[g], q0});
+    DevBuf d_tiles;
+    if (!tiles.empty()) {
+        int rc = dev_upload(d_tiles, tiles.data(), tiles.size() * sizeof(GroupTile));
+        if (rc != SPTAG_AMD_OK) return rc;
+    }
+    int err = launch_group_knn(vt, dm, d_vectors, n, dim, d_members,
+                               d_tiles.as<GroupTile>(), (int32_t)tiles.size(), k, d_vids,
+                               d_dists);
+    if (err != 0) {
+        fprintf(stderr, "sptag_amd: group knn launch failed %d\n", err);
+        return SPTAG_AMD_ERR_INTERNAL;
+    }
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+int sptag_amd_group_knn_device(int device, const void* d_vectors, int valuetype,
+                               int distmethod, int32_t n, int32_t dim,
+                               const int32_t* d_members, int32_t nmembers,
+                               const int32_t* starts, const int32_t* counts, int32_t ngroups,
+                               int32_t k, int32_t* d_out_vids, float* d_out_dists)
+{
+    if (!d_vectors || !d_members || !d_out_vids || !d_out_dists || n < 1 || dim < 1 ||
+        dim > MAX_DIM || (valuetype != VT_FLOAT && valuetype != VT_INT8) ||
+        (distmethod != DM_L2 && distmethod != DM_COSINE) ||
+        (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) ||
+        !group_ranges_ok(nmembers, starts, counts, ngroups, k))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    return group_knn_core(d_vectors, valuetype, distmethod, n, dim, d_members, starts, counts,
+                          ngroups, k, d_out_vids, d_out_dists);
+}
+
+int sptag_amd_group_knn(SptagAmdIndex* ix, const int32_t* members, int32_t nmembers,
+                        const int32_t* starts, const int32_t* counts, int32_t ngroups,
+                        int32_t k, int32_t* out_vids, float* out_dists)
+{
+    if (!ix || !members || !out_vids || !out_dists ||
+        !group_ranges_ok(nmembers, starts, counts, ngroups, k))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available() || !ix->d_vectors) return SPTAG_AMD_ERR_NOGPU;
+    std::lock_guard<std::mutex> g(ix->lock);
+    std::vector<bool> seen((size_t)ix->n, false);
+    for (int32_t i = 0; i < nmembers; i++) {
+        if (members[i] < 0 || members[i] >= ix->n || seen[members[i]])
+            return SPTAG_AMD_ERR_PARAM;
+        seen[members[i]] = true;
+    }
+    HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
+
+    const size_t total = (size_t)ix->n * k;
+    DevBuf d_members;
+    TopkOut out;
+    int rc = nmembers > 0 ? dev_upload(d_members, members, (size_t)nmembers * 4) : SPTAG_AMD_OK;
+    if (rc != SPTAG_AMD_OK) return rc;
+    if ((rc = out.ensure(total)) != SPTAG_AMD_OK) return rc;
+    rc = group_knn_core(ix->d_vectors.as(), ix->vt, ix->dm, ix->n, ix->dim,
+                        d_members.as<int32_t>(), starts, counts, ngroups, k, out.vids(),
+                        out.dists());
+    return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, total);
+}
+
 /* Host-side distance restatements for the add path's edge arithmetic
  * (RebuildNeighbors / InsertNeighbors recompute pair distances on the
  * host, as the reference does on CPU): same rounding contracts as the
