@@ -16,9 +16,8 @@
  * Division of labor inside the wave:
  *   - frontier/tree heaps: the reference's binary heap, comparison for
  *     comparison (pop order on equal keys is part of the parity contract),
- *     evaluated by the whole wave in the batched search (ndheap_*_wave) and
- *     by lane 0 where inserts interleave with other serial work; result-set
- *     mutation -> lane 0, state in LDS;
+ *     evaluated by the whole wave in every kernel (ndheap_*_wave);
+ *     result-set mutation -> lane 0, state in LDS;
  *   - adjacency row load: lanes 0..deg-1, one coalesced 128B line;
  *   - visited-set: per-query open-addressing table in GLOBAL memory
  *     (512KB-class tables do not fit LDS at MaxCheck 8192 — SURVEY.md §7),
@@ -45,22 +44,6 @@ namespace sptag_amd {
 #ifndef SPTAG_LB_WAVES
 #define SPTAG_LB_WAVES 1   /* min waves/SIMD hint; raise to cap VGPRs */
 #endif
-#ifndef SPTAG_WAVE_POP
-#define SPTAG_WAVE_POP 1   /* 0: serial frontier/tree pops (measurement builds) */
-#endif
-/* Loads that depend on nothing but the node a pop is about to return, issued
- * ahead of that pop (peek_frontier). Bit mask, so that measurement builds can
- * take the parts apart: 1 graph row, 2 tree triple. (4, the first chunk of a
- * tree node's children's center ids, issued once the triple is in, was built
- * and lost to the build without it: profiles/pop_ahead_bench.txt.) Serial
- * pops go without. */
-#ifndef SPTAG_POP_AHEAD
-#define SPTAG_POP_AHEAD 3
-#endif
-#if !SPTAG_WAVE_POP
-#undef SPTAG_POP_AHEAD
-#define SPTAG_POP_AHEAD 0
-#endif
 
 static constexpr float MAXDIST = __FLT_MAX__ / 10.0f; /* Common.h:122 */
 
@@ -68,7 +51,7 @@ struct NodeDist { int32_t node; float distance; };
 struct QRes { int32_t vid; float dist; };
 
 /* ------------------------------------------------------------------ *
- * serial structures (lane 0 only), exact reference semantics
+ * frontier / tree heap: storage
  * ------------------------------------------------------------------ */
 
 /* 2^floor(log2(size)) — start of the heap's last level (Heap.h:25) */
@@ -103,82 +86,16 @@ DEV void hset(const HeapRef& h, int i, NodeDist v)
     else h.a[(uint32_t)i] = v;
 }
 
-/* Heap.h:38-62 insert (incl. the full-heap last-level replace path). */
-DEV void ndheap_insert(HeapRef h, int* count, NodeDist v, int* oflow)
-{
-    int loc;
-    if (*count == h.cap) {
-        if (h.cap < h.ref_cap) { *oflow = 1; return; }
-        int lastlevel = heap_lastlevel(h.cap);
-        int maxi = lastlevel;
-        float maxd = hget(h, maxi).distance;
-        for (int i = lastlevel + 1; i <= h.cap; i++) {
-            float di = hget(h, i).distance;
-            if (maxd < di) { maxi = i; maxd = di; }
-        }
-        if (v.distance > maxd) return;
-        loc = maxi;
-    } else {
-        loc = ++(*count);
-    }
-    int par = loc >> 1;
-    while (par > 0) {
-        NodeDist p = hget(h, par);
-        if (!(v.distance < p.distance)) break;
-        hset(h, loc, p);
-        loc = par;
-        par >>= 1;
-    }
-    hset(h, loc, v);
-}
-
-/* Heap.h:90-105 heapify + :74-82 pop. The sinking element is the original
- * root value throughout (the reference swaps it level by level), so it is
- * carried in a register instead of re-read. */
-DEV void ndheap_heapify(HeapRef h, int count)
-{
-    int parent = 1, next = 2;
-    if (next > count) return;
-    NodeDist pv = hget(h, parent);
-    while (next < count) {
-        NodeDist nv = hget(h, next);
-        NodeDist nv2 = hget(h, next + 1);
-        if (nv.distance > nv2.distance) { next++; nv = nv2; }
-        if (nv.distance < pv.distance) {
-            hset(h, parent, nv);
-            hset(h, next, pv);
-            parent = next;
-            next <<= 1;
-        } else {
-            return;
-        }
-    }
-    if (next == count) {
-        NodeDist nv = hget(h, next);
-        if (nv.distance < pv.distance) {
-            hset(h, parent, nv);
-            hset(h, next, pv);
-        }
-    }
-}
-
-DEV NodeDist ndheap_pop(HeapRef h, int* count)
-{
-    if (*count == 0) return hget(h, 0);
-    NodeDist top = hget(h, 1);
-    hset(h, 1, hget(h, *count));
-    /* the vacated slot beyond count is dead until the next insert writes
-     * it (Heap.h swaps the old top there; nothing ever reads it) */
-    (*count)--;
-    ndheap_heapify(h, *count);
-    return top;
-}
-
 DEV NodeDist ndheap_top(HeapRef h, int count) { return count == 0 ? hget(h, 0) : hget(h, 1); }
 
 /* ------------------------------------------------------------------ *
- * the same heap, evaluated by the whole wave: same comparisons on the
- * same array, so the array after every operation is the serial one's
+ * heap operations, evaluated by the whole wave: the comparisons of
+ * Heap.h's insert and pop on the same array, so the array after every
+ * operation is the serial one's (the line-by-line serial restatement
+ * that the heap probe compares these with stands next to the probe).
+ * Every search kernel mutates its heaps through these alone: counts are
+ * wave-uniform, lane 0 keeps them in LDS between phases, and heap_fence
+ * is the one ordering argument.
  * ------------------------------------------------------------------ */
 
 /* v broadcast from lane l (wave-uniform l) */
@@ -309,6 +226,12 @@ DEV NodeDist ndheap_pop_wave(HeapRef h, int& count)
     heap_fence();
     return top;
 }
+
+/* ------------------------------------------------------------------ *
+ * what stays serial (lane 0 only), exact reference semantics: the result
+ * set (qrs_*), the iterator's results queue (dpq_insert) and the visited
+ * claims whose order the reference fixes (tree centers, duplicate chains)
+ * ------------------------------------------------------------------ */
 
 /* DistPriorityQueue (WorkSpace.h:167-225): 1-based bounded float max-heap
  * seeded with MaxDist; len starts at 1. */
@@ -655,10 +578,11 @@ DEV float ref_dist_grp(const T* q, const T* v, int d)
 
 /* Per-phase cycle marks, diagnostic builds only; every member is empty
  * without PROF. One wave per workgroup, so lane-0 clock64 spans are
- * wave-accurate. With SPTAG_POP_AHEAD the `pop` span takes in the row's
- * latency and the SPT-pop span the tree triple's, so `pop + row` and the
- * seed / tree totals are what compare with a build without it, not the
- * single lines. */
+ * wave-accurate. A pop's dependent loads are issued ahead of it
+ * (peek_frontier), so the `pop` span takes in the row's latency and the
+ * SPT-pop span the tree triple's: `pop + row` and the seed / tree totals
+ * are what compare with the profiles from before that, not the single
+ * lines. */
 template <bool PROF>
 struct PhaseClock {
     uint64_t pc[9] = {};
@@ -701,9 +625,7 @@ struct SerialState {          /* in LDS; lane 0 writes, wave reads after sync */
     int checked;
     int oflow, terminate, break_flag, want_tree;
     int tree_checked, no_better;   /* KDT counters */
-    float fbcast;                  /* KDT upper-bound broadcast */
-    NodeDist popped;
-    int relaxed;                   /* iterative: sticky relaxedMono flag */
+    int relaxed;                  /* iterative: sticky relaxedMono flag */
 };
 static_assert(sizeof(SerialState) <= SERIAL_STATE_BYTES,
               "SerialState outgrew its LDS slot");
@@ -876,7 +798,7 @@ DEV void stage_dists(QCtx<T>& c, int cnt)
  * slots of heap `h` holding `count` entries (slot for the i-th insert is
  * count+1+i while the heap is not full, and the warm is advisory: a wrong
  * slot guess only wastes a touch; slots past the capacity are not guessed).
- * Lane-0's serial percolate-up then reads L1/L2-warm lines instead of
+ * The inserts' ancestor reads then hit L1/L2-warm lines instead of
  * paying an HBM round trip per level — the seed phase was 31% of kernel
  * cycles with cold SPT parent reads. Levels in the LDS tier are skipped. */
 DEV void heap_warm_parents(const HeapRef& h, int count, int cnt)
@@ -916,20 +838,13 @@ DEV void stage_child_dists(QCtx<T>& c, int base, int cnt)
 DEV int uniform_count(const int* p) { return __builtin_amdgcn_readfirstlane(*p); }
 
 /* Pop heap `h`, whose count lane 0 keeps at *pcount; the old top comes back
- * on every lane. The serial form (SPTAG_WAVE_POP=0, measurement builds) goes
- * through ss->popped and a barrier. */
-DEV NodeDist pop_frontier(HeapRef h, int* pcount, SerialState* ss)
+ * on every lane. */
+DEV NodeDist pop_frontier(HeapRef h, int* pcount)
 {
-#if SPTAG_WAVE_POP
     int n = uniform_count(pcount);
     NodeDist top = ndheap_pop_wave(h, n);
     if (threadIdx.x == 0) *pcount = n;
     return top;
-#else
-    if (threadIdx.x == 0) ss->popped = ndheap_pop(h, pcount);
-    __syncthreads();
-    return ss->popped;
-#endif
 }
 
 /* The node the next pop_frontier of `h` returns, wave-uniform; the heap is
@@ -938,7 +853,12 @@ DEV NodeDist pop_frontier(HeapRef h, int* pcount, SerialState* ss)
  * be issued ahead of the pop and come back under its own waits: vector
  * memory loads return in the order they were issued, so the pop's wait for
  * its next block covers them. The entry sits in the LDS tier where there is
- * one, else in the line that the pop's first block reads. */
+ * one, else in the line that the pop's first block reads. bkt_search_kernel
+ * issues the graph row this way and search_trees_dev the tree triple. A
+ * third part,
+ * the first chunk of a tree node's children's center ids issued once the
+ * triple is in, was built and lost to the build without it
+ * (profiles/pop_ahead_bench.txt). */
 DEV int32_t peek_frontier(const HeapRef& h)
 {
     return __builtin_amdgcn_readfirstlane(hget(h, 1).node);
@@ -986,24 +906,16 @@ DEV void search_trees_dev(QCtx<T>& c, int limit, PhaseClock<PROF>& clk)
         __syncthreads();
         if (c.ss->spt_count <= 0 || c.ss->oflow) break;
         clk.aux_begin();
-#if SPTAG_POP_AHEAD & 2
         /* the node about to be popped: its triple on lanes 0..2, issued
          * ahead of the pop */
         const int32_t* tn = di.tree_nodes + (size_t)peek_frontier(c.spt) * 3;
         int32_t tri = 0;
         if (c.lane < 3) tri = tn[c.lane];
-        NodeDist bcell = pop_frontier(c.spt, &c.ss->spt_count, c.ss);
+        NodeDist bcell = pop_frontier(c.spt, &c.ss->spt_count);
         clk.aux_end(1);
         int32_t center = __builtin_amdgcn_readlane(tri, 0);
         int32_t cs = __builtin_amdgcn_readlane(tri, 1);
         int32_t ce = __builtin_amdgcn_readlane(tri, 2);
-#else
-        NodeDist bcell = pop_frontier(c.spt, &c.ss->spt_count, c.ss);
-        clk.aux_end(1);
-        int32_t center = di.tree_nodes[(size_t)bcell.node * 3 + 0];
-        int32_t cs = di.tree_nodes[(size_t)bcell.node * 3 + 1];
-        int32_t ce = di.tree_nodes[(size_t)bcell.node * 3 + 2];
-#endif
         if (cs < 0) {
             clk.aux_begin();
             const int checked = uniform_count(&c.ss->checked) +
@@ -1146,19 +1058,12 @@ void bkt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
         __syncthreads();
         if (ss->ng_count <= 0 || ss->terminate || ss->oflow) break;
         clk.mark();
-#if SPTAG_POP_AHEAD & 1
         /* the row of the node about to be popped, issued ahead of the pop */
         const int32_t nn = load_row_lanes(c, peek_frontier(c.ng));
-        const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count, ss);
+        const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count);
         clk.acc(1);
         popped++;
         const Row row = make_row(c, nn);
-#else
-        const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count, ss);
-        clk.acc(1);
-        popped++;
-        const Row row = load_row(c, gnode.node);
-#endif
         clk.acc(2);
 
         if (lane == 0) {
@@ -1305,54 +1210,68 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
     for (;;) {
         __syncthreads();
         if (ss->ng_count <= 0 || ss->oflow || count >= batch) break;
-        if (lane == 0) ss->popped = ndheap_pop(c.ng, &ss->ng_count);
-        __syncthreads();
-        NodeDist gnode = ss->popped;
+        const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count);
         const Row row = load_row(c, gnode.node);
 
-        if (lane == 0) {
-            int cnt_new = count;
-            if (not_deleted(di, gnode.node)) {
-                qrs_add(qrs, batch, gnode.node, gnode.distance);
-                cnt_new = count + 1;
-                if (gnode.distance > dpq[1] || ss->checked > cfg.max_check)
-                    ss->relaxed = 1;                     /* relaxedMono */
-            }
-            ss->fbcast = __int_as_float(cnt_new);
+        int cnt_new = count;
+        if (lane == 0 && not_deleted(di, gnode.node)) {
+            qrs_add(qrs, batch, gnode.node, gnode.distance);
+            cnt_new = count + 1;
+            if (gnode.distance > dpq[1] || ss->checked > cfg.max_check)
+                ss->relaxed = 1;                     /* relaxedMono */
         }
-        __syncthreads();
-        count = __float_as_int(ss->fbcast);
+        count = __builtin_amdgcn_readfirstlane(cnt_new);
 
         if (row.checkNode < -1) {
             /* iterative duplicate chain (BKTIndex.cpp:387-405): duplicates
-             * enter the frontier; stage chunk distances, lane 0 inserts */
+             * enter the frontier. Stage a chunk's distances; lane 0 decides
+             * candidate by candidate in chunk order (one lane's visited
+             * claims in order are what the reference does); the wave inserts
+             * the accepted ones, in chunk order too. */
             const int32_t* tn = &di.tree_nodes[(size_t)(-2 - row.checkNode) * 3];
             int32_t cs0 = -tn[1], ce0 = tn[2];
             for (int base = cs0; base < ce0; base += 64) {
                 int cnt = min(64, ce0 - base);
                 stage_child_dists<T, DM, DC, false>(c, base, cnt);
+                uint32_t lo = 0, hi = 0;
                 if (lane == 0) {
                     for (int i = 0; i < cnt; i++) {
                         int32_t tmpNode = c.istage[i];
-                        if (!not_deleted(di, tmpNode)) continue;
-                        if (!visited_test_insert(c.vtab, c.vmask, tmpNode, &ss->oflow))
-                            ndheap_insert(c.ng, &ss->ng_count,
-                                          NodeDist{tmpNode, c.dstage[i]}, &ss->oflow);
+                        if (not_deleted(di, tmpNode) &&
+                            !visited_test_insert(c.vtab, c.vmask, tmpNode, &ss->oflow))
+                            (i < 32 ? lo : hi) |= 1u << (i & 31);
                     }
                 }
+                const uint64_t acc =
+                    (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hi) << 32 |
+                    (uint32_t)__builtin_amdgcn_readfirstlane(lo);
+                const NodeDist cand{lane < cnt ? c.istage[lane] : -1,
+                                    lane < cnt ? c.dstage[lane] : MAXDIST};
+                int ngc = uniform_count(&ss->ng_count);
+                for (uint64_t m = acc; m; m &= m - 1)
+                    ndheap_insert_wave(c.ng, ngc, lane_bcast(cand, __builtin_ctzll(m)),
+                                       &ss->oflow);
+                if (lane == 0) ss->ng_count = ngc;
                 __syncthreads();
             }
         }
 
+        /* BKTIndex.cpp:406-415: every computed neighbor joins the frontier,
+         * in row order, wave-wide; lane 0 feeds the results queue. The queue
+         * is independent of the NG heap: nothing between two NG inserts
+         * reads it or `checked`. */
         int ncand = expand_neighbors(c, row);
         stage_dists<T, DM, DC>(c, ncand);
+        const NodeDist cand{lane < ncand ? c.istage[lane] : -1,
+                            lane < ncand ? c.dstage[lane] : MAXDIST};
+        int ngc = uniform_count(&ss->ng_count);
+        for (int r = 0; r < ncand; r++)
+            ndheap_insert_wave(c.ng, ngc, lane_bcast(cand, r), &ss->oflow);
         if (lane == 0) {
-            for (int r = 0; r < ncand; r++) {
-                float dv = c.dstage[r];
-                ss->checked++;
-                ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], dv}, &ss->oflow);
-                dpq_insert(dpq, &ss->dpq_len, cfg.dpq_cap, dv);
-            }
+            ss->ng_count = ngc;
+            ss->checked += ncand;
+            for (int r = 0; r < ncand; r++)
+                dpq_insert(dpq, &ss->dpq_len, cfg.dpq_cap, c.dstage[r]);
             ss->want_tree = (ndheap_top(c.ng, ss->ng_count).distance >
                              ndheap_top(c.spt, ss->spt_count).distance);
         }
@@ -1388,42 +1307,45 @@ void bkt_iter_kernel(DevIndex di, SearchCfg cfg, IterBufs ib, int batch)
 
 struct KdtNode { int32_t left, right, split_dim; float split_value; };
 
-/* KDTree.h:234-271 KDTSearch, iterative; lane 0 descends (serial pointer
- * chase), the wave's first 16-lane group computes the leaf distance. */
+/* KDTree.h:234-271 KDTSearch, iterative. The descent is wave-uniform (`node`
+ * and `dist_bound` are): every lane reads the same tree node, one broadcast
+ * load, and computes the same bound with the same expression, and the
+ * `other` sides go into the tree heap back to back under one count. Lane 0
+ * claims the leaf in the visited table, the wave's first 16-lane group
+ * computes its distance, the wave inserts it. Ends in the barrier that
+ * publishes the counters. */
 template <typename T, int DM, int DC>
 DEV void kdt_search_node_dev(QCtx<T>& c, int32_t node, float dist_bound)
 {
     const DevIndex& di = *c.di;
     const KdtNode* kn = (const KdtNode*)di.tree_nodes;
     SerialState* ss = c.ss;
-    /* descent: lane 0 walks, broadcasting the final leaf via ss->popped */
-    if (c.lane == 0) {
-        while (node >= 0) {
-            KdtNode tn = kn[node];
-            float qv = (float)c.qlds[tn.split_dim];
-            float diff = qv - tn.split_value;
-            float other_bound = dist_bound + diff * diff;
-            int32_t best = diff < 0.0f ? tn.left : tn.right;
-            int32_t other = diff < 0.0f ? tn.right : tn.left;
-            ndheap_insert(c.spt, &ss->spt_count, NodeDist{other, other_bound},
-                          &ss->oflow);
-            node = best;
-        }
-        int32_t index = -node - 1;
-        if (index >= di.n) index = -1;
-        else if (visited_test_insert(c.vtab, c.vmask, index, &ss->oflow)) index = -1;
-        ss->popped.node = index;
+    int n = uniform_count(&ss->spt_count);
+    while (node >= 0) {
+        KdtNode tn = kn[node];
+        float qv = (float)c.qlds[tn.split_dim];
+        float diff = qv - tn.split_value;
+        float other_bound = dist_bound + diff * diff;
+        int32_t best = diff < 0.0f ? tn.left : tn.right;
+        int32_t other = diff < 0.0f ? tn.right : tn.left;
+        ndheap_insert_wave(c.spt, n, NodeDist{other, other_bound}, &ss->oflow);
+        node = __builtin_amdgcn_readfirstlane(best);   /* uniform by construction */
     }
-    __syncthreads();
-    int32_t index = ss->popped.node;
-    if (index >= 0) {
+    if (c.lane == 0) ss->spt_count = n;
+    const int32_t index = -node - 1;
+    int seen = 1;
+    if (c.lane == 0 && index < di.n)
+        seen = visited_test_insert(c.vtab, c.vmask, index, &ss->oflow);
+    if (!__builtin_amdgcn_readfirstlane(seen)) {
         float dv = 0.0f;
         if (c.lane < 16)
             dv = ref_dist_grp<T, DM, DC>(c.qlds, vec_at<T>(di, index), di.dim);
+        int ngc = uniform_count(&ss->ng_count);
+        ndheap_insert_wave(c.ng, ngc, NodeDist{index, lane_bcast(dv, 0)}, &ss->oflow);
         if (c.lane == 0) {
             ss->tree_checked++;
             ss->checked++;
-            ndheap_insert(c.ng, &ss->ng_count, NodeDist{index, dv}, &ss->oflow);
+            ss->ng_count = ngc;
         }
     }
     __syncthreads();
@@ -1437,9 +1359,7 @@ DEV void kdt_search_trees_dev(QCtx<T>& c, int limits)
     for (;;) {
         __syncthreads();
         if (ss->spt_count <= 0 || ss->checked >= limits || ss->oflow) break;
-        if (c.lane == 0) ss->popped = ndheap_pop(c.spt, &ss->spt_count);
-        __syncthreads();
-        NodeDist tcell = ss->popped;
+        const NodeDist tcell = pop_frontier(c.spt, &ss->spt_count);
         kdt_search_node_dev<T, DM, DC>(c, tcell.node, tcell.distance);
     }
     __syncthreads();
@@ -1474,12 +1394,11 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
     for (;;) {
         __syncthreads();
         if (ss->ng_count <= 0 || ss->terminate || ss->oflow) break;
-        if (lane == 0) ss->popped = ndheap_pop(c.ng, &ss->ng_count);
-        __syncthreads();
+        const NodeDist gnode = pop_frontier(c.ng, &ss->ng_count);
         popped++;
-        NodeDist gnode = ss->popped;
         const Row row = load_row(c, gnode.node);
 
+        float upper_bound = 0.0f;
         if (lane == 0) {
             /* KDTIndex.cpp:201-209: result + budget termination */
             if (not_deleted(di, gnode.node)) {
@@ -1488,24 +1407,26 @@ void kdt_search_kernel(DevIndex di, SearchCfg cfg, SearchBufs bufs)
                     ss->terminate = 1;
             }
             float worst = qrs[0].dist;
-            ss->fbcast = worst > gnode.distance ? worst : gnode.distance;
+            upper_bound = worst > gnode.distance ? worst : gnode.distance;
         }
         __syncthreads();
         if (ss->terminate) break;
-        float upper_bound = ss->fbcast;
+        upper_bound = lane_bcast(upper_bound, 0);
 
         int ncand = expand_neighbors(c, row);
         stage_dists<T, DM, DC>(c, ncand);
+        /* KDTIndex.cpp:211-233: every computed neighbor joins the frontier,
+         * in row order, wave-wide; track whether any beat the upper bound.
+         * Nothing reads `checked` inside a row. */
+        const NodeDist cand{lane < ncand ? c.istage[lane] : -1,
+                            lane < ncand ? c.dstage[lane] : MAXDIST};
+        int ngc = uniform_count(&ss->ng_count);
+        for (int r = 0; r < ncand; r++)
+            ndheap_insert_wave(c.ng, ngc, lane_bcast(cand, r), &ss->oflow);
+        const bool local_opt = !__ballot(lane < ncand && cand.distance <= upper_bound);
         if (lane == 0) {
-            /* KDTIndex.cpp:211-233: every computed neighbor joins the
-             * frontier; track whether any beat the upper bound */
-            int local_opt = 1;
-            for (int r = 0; r < ncand; r++) {
-                float dv = c.dstage[r];
-                if (dv <= upper_bound) local_opt = 0;
-                ss->checked++;
-                ndheap_insert(c.ng, &ss->ng_count, NodeDist{c.istage[r], dv}, &ss->oflow);
-            }
+            ss->ng_count = ngc;
+            ss->checked += ncand;
             if (local_opt) ss->no_better++;
             else ss->no_better = 0;
             ss->want_tree = 0;
@@ -1737,7 +1658,82 @@ int launch_merge_topk(const int32_t* vids, const float* dists,
  * heap probe (tests): one script of inserts and pops on a HeapRef built
  * from the arguments, run by block 0 with the serial functions and by
  * block 1 with the wave-wide ones, each on its own array.
+ *
+ * The serial functions are Heap.h restated line by line for one lane. No
+ * search kernel calls them: they are the reference that the probe holds
+ * ndheap_insert_wave and ndheap_pop_wave to.
  * ------------------------------------------------------------------ */
+
+/* Heap.h:38-62 insert (incl. the full-heap last-level replace path). */
+DEV void ndheap_insert(HeapRef h, int* count, NodeDist v, int* oflow)
+{
+    int loc;
+    if (*count == h.cap) {
+        if (h.cap < h.ref_cap) { *oflow = 1; return; }
+        int lastlevel = heap_lastlevel(h.cap);
+        int maxi = lastlevel;
+        float maxd = hget(h, maxi).distance;
+        for (int i = lastlevel + 1; i <= h.cap; i++) {
+            float di = hget(h, i).distance;
+            if (maxd < di) { maxi = i; maxd = di; }
+        }
+        if (v.distance > maxd) return;
+        loc = maxi;
+    } else {
+        loc = ++(*count);
+    }
+    int par = loc >> 1;
+    while (par > 0) {
+        NodeDist p = hget(h, par);
+        if (!(v.distance < p.distance)) break;
+        hset(h, loc, p);
+        loc = par;
+        par >>= 1;
+    }
+    hset(h, loc, v);
+}
+
+/* Heap.h:90-105 heapify + :74-82 pop. The sinking element is the original
+ * root value throughout (the reference swaps it level by level), so it is
+ * carried in a register instead of re-read. */
+DEV void ndheap_heapify(HeapRef h, int count)
+{
+    int parent = 1, next = 2;
+    if (next > count) return;
+    NodeDist pv = hget(h, parent);
+    while (next < count) {
+        NodeDist nv = hget(h, next);
+        NodeDist nv2 = hget(h, next + 1);
+        if (nv.distance > nv2.distance) { next++; nv = nv2; }
+        if (nv.distance < pv.distance) {
+            hset(h, parent, nv);
+            hset(h, next, pv);
+            parent = next;
+            next <<= 1;
+        } else {
+            return;
+        }
+    }
+    if (next == count) {
+        NodeDist nv = hget(h, next);
+        if (nv.distance < pv.distance) {
+            hset(h, parent, nv);
+            hset(h, next, pv);
+        }
+    }
+}
+
+DEV NodeDist ndheap_pop(HeapRef h, int* count)
+{
+    if (*count == 0) return hget(h, 0);
+    NodeDist top = hget(h, 1);
+    hset(h, 1, hget(h, *count));
+    /* the vacated slot beyond count is dead until the next insert writes
+     * it (Heap.h swaps the old top there; nothing ever reads it) */
+    (*count)--;
+    ndheap_heapify(h, *count);
+    return top;
+}
 
 __global__ __launch_bounds__(64)
 void heap_probe_kernel(HeapProbeArgs p)

@@ -274,3 +274,74 @@ def test_gpu_iter_saturation_is_an_error(capfd):
     with pytest.raises(SptagAmdError):      # sticky
         it.Next(8)
     it.Close()
+
+
+# ---- frontier heap full at the reference's capacity ---------------------
+
+FULL_MC = 4                        # NG heap 30 * 4 = 120 entries, tree heap 40
+FULL_BATCHES = [8] * 8
+# queries of f32_l2_chain next to or on the chains of 38 and 18 copies
+FULL_CHAIN_QUERIES = [1, 2, 4, 5]
+
+
+def _full_case(kind):
+    """(case or None, index folder or None, queries, graph, oracle calls)."""
+    key = ("full", kind)
+    if key not in _ref:
+        if kind == "built":
+            c = built_case(SAT_N, 16, "f32", "L2", nq=2)
+            oix, q, graph, src = orc_from_case(c), c["q"], c["args"][3], c
+        else:
+            g = load_golden("f32_l2_chain")
+            oix, q = OrcIndex.load(g["index"]), g["queries"][FULL_CHAIN_QUERIES]
+            graph, src = read_index_arrays(g["index"], np.float32)[3], g["index"]
+        _ref[key] = (src, q, graph, orc_iter_run(oix, q, FULL_MC, FULL_BATCHES))
+    return _ref[key]
+
+
+def _first_full_pop(graph, ids, cap):
+    """Every id a popped node's row names has been visited, and an id enters
+    the frontier exactly once, when it is first visited; every popped id was
+    inserted before. So after p pops the heap has seen at least |U_p| inserts,
+    U_p = the first p popped ids and everything their rows name, and had it
+    never been full it would hold at least |U_p| - p entries. The first p
+    with |U_p| - p > cap: an insert met the full heap before pop p ended."""
+    seen = set()
+    for p, v in enumerate(ids.tolist(), 1):
+        seen.add(v)
+        seen.update(x for x in graph[v].tolist() if x >= 0)
+        if len(seen) - p > cap:
+            return p
+    return None
+
+
+@pytest.mark.parametrize("kind", ["built", "chain"])
+def test_oracle_iter_fills_the_frontier_heap(kind):
+    """At MaxCheck 4 the iterator's frontier heap (30 * MaxCheck = 120) has
+    met an insert while full before the last Next(8) of every query (the
+    bound is a lower one: it leaves out what the tree and the chains add),
+    so at least one whole call pops after the last-level scan. The chain
+    queries return copies, which only the duplicate-chain walk puts into the
+    frontier."""
+    _, q, graph, calls = _full_case(kind)
+    for i in range(len(q)):
+        ids = _stream(calls, i)
+        assert len(ids) == sum(FULL_BATCHES)
+        p = _first_full_pop(graph, ids, 30 * FULL_MC)
+        print(f"{kind} query {i}: full by pop {p} of {len(ids)}")
+        assert p is not None and p <= len(ids) - 8, f"{kind} query {i}: {p}"
+    if kind == "chain":
+        for i in range(len(q)):
+            # a copy is named by no graph row
+            assert not np.isin(_stream(calls, i), graph).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["built", "chain"])
+def test_gpu_iter_full_frontier_heap(kind):
+    from sptag_amd import AnnIndex
+    src, q, _, calls = _full_case(kind)
+    ix = gpu_from_case(src) if kind == "built" else AnnIndex.Load(src)
+    it = ix.Iterate(q, max_check=FULL_MC)
+    assert_iter_calls_equal(it, calls, FULL_BATCHES, f"full heap {kind}")
+    it.Close()

@@ -1,6 +1,6 @@
 """The batched and iterative BKT kernels read the top of a heap before they
 pop it and issue the loads that follow from that node alone ahead of the pop
-(kernels.hip, peek_frontier / SPTAG_POP_AHEAD): the adjacency row in the graph
+(kernels.hip, peek_frontier): the adjacency row in the graph
 loop and the tree node's triple in the tree descent. The traversal must not
 change, so every case compares ids and float bits with the oracle:
 

@@ -194,3 +194,84 @@ def test_kdt_builder_single_point_tree_terminates():
     assert start.tolist() == [0] and nodes.shape == (1, 4)
     assert nodes[0, 0] == -1          # leaf of vector 0
     assert nodes[0, 1] == -2          # empty side: id n, ignored by search
+
+
+# ---- KDT: a descent of more than 31 levels, rows with no candidate ------
+
+DEEP_N, DEEP_LEVELS = 300, 48
+
+
+def _deep_kdt_case():
+    """built_case(300) KDT under two hand-made trees (the builder's are
+    balanced, 14 levels at 4000 rows). Tree 0 splits on dimension 0 at
+    rising values: each inner node has the leaf of the next row, in order of
+    x[:, 0], on its left and the next inner node on its right, so a query
+    beyond the last split walks all 48 nodes and pushes 48 `other` bounds
+    before it reaches a leaf. Tree 1 is the mirror image on dimension 1
+    (inner node on the left, values falling). Two queries are added to the
+    case's eight: one walks both trees to the end, one leaves both at the
+    root."""
+    if "deep" not in _ref:
+        c = built_case(DEEP_N, 16, "f32", "L2", "KDT")
+        vec, _, _, graph, dm = c["args"]
+        nodes = np.empty((2 * DEEP_LEVELS, 4), dtype=np.int32)
+        splits = np.empty(2 * DEEP_LEVELS, dtype=np.float32)
+        for t, (dim, sign) in enumerate([(0, 1), (1, -1)]):
+            order = np.argsort(sign * vec[:, dim], kind="stable")[:DEEP_LEVELS + 1]
+            for j in range(DEEP_LEVELS):
+                i = t * DEEP_LEVELS + j
+                leaf = -int(order[j]) - 1
+                nxt = i + 1 if j + 1 < DEEP_LEVELS else -int(order[j + 1]) - 1
+                nodes[i, :3] = (leaf, nxt, dim) if sign > 0 else (nxt, leaf, dim)
+                splits[i] = (vec[order[j], dim] + vec[order[j + 1], dim]) / np.float32(2)
+        nodes[:, 3] = splits.view(np.int32)
+        nodes.setflags(write=False)
+        tstart = np.array([0, DEEP_LEVELS], dtype=np.int32)
+        tstart.setflags(write=False)
+        far = np.zeros((2, 16), dtype=np.float32)
+        far[0, 0], far[0, 1] = 10, -10        # beyond every split of both trees
+        far[1, 0], far[1, 1] = -10, 10        # before the first split of both
+        q = np.concatenate([c["q"], far])
+        q.setflags(write=False)
+        case = dict(c, args=(vec, tstart, nodes.reshape(-1), graph, dm), q=q)
+        oix = orc_from_case(case)
+        ref = {(k, mc): oix.search_batch(q, k, mc)
+               for k in (1, DEEP_N + 3) for mc in (64, 8192)}
+        _ref["deep"] = (case, nodes, splits, ref)
+    return _ref["deep"]
+
+
+def _descent_levels(nodes, splits, root, q):
+    """inner nodes that KDTSearch walks from `root`: one `other` push each"""
+    node, levels = root, 0
+    while node >= 0:
+        diff = np.float32(q[nodes[node, 2]]) - splits[node]
+        node = nodes[node, 0] if diff < 0 else nodes[node, 1]
+        levels += 1
+    return levels
+
+
+def test_oracle_deep_kdt_case_is_deep_and_runs_dry():
+    case, nodes, splits, ref = _deep_kdt_case()
+    q = case["q"]
+    lv = np.array([[_descent_levels(nodes, splits, r, x) for r in case["args"][1]]
+                   for x in q])
+    assert (lv[-2] == DEEP_LEVELS).all() and (lv[-1] == 1).all()
+    assert lv.max() > 31 and ((lv > 1) & (lv < DEEP_LEVELS)).any()
+    # k above n: the result set never fills, so nothing ends the search but
+    # an empty frontier, and every row is popped. When the last one is, all
+    # 300 ids are visited: that pop, at the least, finds no candidate.
+    ov, od = ref[(DEEP_N + 3, 8192)]
+    _check_padding(ov, od, DEEP_N)
+    # and k = 1 stops long before that
+    assert (ref[(1, 64)][0] >= 0).all()
+
+
+@pytest.mark.gpu
+def test_gpu_deep_kdt_descent_and_empty_rows():
+    case, _, _, ref = _deep_kdt_case()
+    ix = gpu_from_case(case)
+    for (k, mc), (ov, od) in ref.items():
+        gv, gd = ix.BatchSearch(case["q"], k, mc)
+        np.testing.assert_array_equal(gv, ov, err_msg=f"k={k} mc={mc} ids")
+        np.testing.assert_array_equal(gd, od, err_msg=f"k={k} mc={mc} dists")
