@@ -171,6 +171,52 @@ int sptag_amd_group_knn_device(int device, const void* d_vectors, int valuetype,
                                int32_t ngroups, int32_t k, int32_t* d_out_vids,
                                float* d_out_dists);
 
+/* RNG prune: the reference's RebuildNeighbors rule
+ * (RelativeNeighborhoodGraph.h:18-35) over caller-supplied candidate lists,
+ * the step that ends every graph stage of the index builder. Row r has a node
+ * id nodes[r] and the list cand_ids[r][0..ncand) with cand_dists[r][0..ncand),
+ * given in ascending distance and never recomputed. The list is walked in
+ * order while fewer than `degree` candidates are accepted:
+ *   - a candidate whose id is < 0 or equals nodes[r], or whose distance is
+ *     not finite, is skipped;
+ *   - candidate c is rejected if some already accepted a has
+ *     rng_factor * dist(a, c) < cand_dists[c] (an f32 product, strict <);
+ *   - otherwise it is accepted.
+ * dist is the search paths' distance for the value type and metric, bit for
+ * bit: f32 in the reference's 16/8/4-accumulator order (1 - dot for cosine),
+ * int8 exact integers (16129 - dot for cosine). Ids are not deduplicated: the
+ * rule decides a repeated id. out_graph[r][0..degree) receives the accepted
+ * ids in list order, then -1. With fill_pruned != 0 a row that ends short of
+ * `degree` also keeps its degree - count nearest valid rejected candidates,
+ * and every kept id, accepted or filled, is written in list order.
+ * 1 <= ncand <= 1024, 1 <= degree <= 64, any nrows >= 1. The handle form
+ * takes host arrays and uses the handle's vectors, value type and metric; the
+ * delete set, the tree and the graph are not consulted (BKT and KDT handles
+ * alike). Computed by the prune kernels of exact.hip: a workgroup owns a row,
+ * keeps the accepted vectors in LDS and streams the list in tiles, each
+ * candidate vector read once. Returns SPTAG_AMD_ERR_PARAM, with the output
+ * untouched, for a null pointer, nrows < 1, ncand or degree out of range, an
+ * rng_factor that is not finite and positive, a node outside [0, n) and a
+ * candidate id >= n. */
+int sptag_amd_rng_prune(SptagAmdIndex* idx, const int32_t* nodes, int32_t nrows,
+                        const int32_t* cand_ids, const float* cand_dists, int32_t ncand,
+                        int32_t degree, float rng_factor, int32_t fill_pruned,
+                        int32_t* out_graph);
+/* The same without a handle: d_vectors ([n][dim] of valuetype), d_nodes, the
+ * lists and the output are HIP device buffers on `device`. It checks what the
+ * host can see (the pointers, nrows, ncand, degree, rng_factor, value type,
+ * metric, 1 <= dim <= 4096, the int8 dim guard of the create calls) and
+ * returns SPTAG_AMD_ERR_PARAM for those. That every node and every candidate
+ * id >= 0 is inside [0, n) is the CALLER'S to guarantee: an id outside makes
+ * the kernels read outside d_vectors. Runs on the default stream and returns
+ * after a device synchronise. */
+int sptag_amd_rng_prune_device(int device, const void* d_vectors, int valuetype,
+                               int distmethod, int32_t n, int32_t dim,
+                               const int32_t* d_nodes, int32_t nrows,
+                               const int32_t* d_cand_ids, const float* d_cand_dists,
+                               int32_t ncand, int32_t degree, float rng_factor,
+                               int32_t fill_pruned, int32_t* d_out_graph);
+
 /* Iterative (streaming) search — mirrors the reference's ResultIterator /
  * SearchIndexIterativeNext protocol (inc/Core/VectorIndex.h:43-49,
  * src/Core/ResultIterator.cpp) over a BATCH of nq per-query iterators whose

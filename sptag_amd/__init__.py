@@ -16,6 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "group_knn_device",
+           "rng_prune_device",
            "MetadataSet", "load_library", "gpu_available", "SptagAmdError"]
 
 _LIB = None
@@ -87,6 +88,17 @@ def load_library():
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
         ctypes.c_void_p, ctypes.c_void_p]
+    lib.sptag_amd_rng_prune.restype = ctypes.c_int
+    lib.sptag_amd_rng_prune.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+        ctypes.c_int32, ctypes.c_void_p]
+    lib.sptag_amd_rng_prune_device.restype = ctypes.c_int
+    lib.sptag_amd_rng_prune_device.argtypes = [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+        ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]
     lib.sptag_amd_save_index.restype = ctypes.c_int
     lib.sptag_amd_save_index.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     for f in ["num_vectors", "dim", "valuetype", "distmethod", "degree",
@@ -377,6 +389,33 @@ class AnnIndex:
             raise SptagAmdError(rc, "group_knn")
         return vids, dists
 
+    def RngPrune(self, nodes, cand_ids, cand_dists, degree, rng_factor=1.0,
+                 fill_pruned=False):
+        """The reference's RebuildNeighbors over candidate lists: row r walks
+        cand_ids[r] (ascending cand_dists[r], never recomputed) and accepts a
+        valid candidate (id >= 0, not nodes[r], finite distance) unless an
+        accepted a has rng_factor * dist(a, c) < cand_dists[r][c], up to
+        `degree`; dist is the handle's search distance. Returns int32
+        [nrows, degree]: the accepted ids in list order, -1 padded; with
+        fill_pruned a short row keeps its nearest rejected candidates too."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        cand_ids = np.ascontiguousarray(cand_ids, dtype=np.int32)
+        cand_dists = np.ascontiguousarray(cand_dists, dtype=np.float32)
+        if (nodes.ndim != 1 or cand_ids.ndim != 2 or
+                cand_ids.shape != cand_dists.shape or
+                cand_ids.shape[0] != nodes.size):
+            raise ValueError("nodes [nrows], cand_ids and cand_dists "
+                             "[nrows, ncand] expected")
+        out = np.empty((nodes.size, max(int(degree), 0)), dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = self._lib.sptag_amd_rng_prune(
+            self._h, p(nodes), nodes.size, p(cand_ids), p(cand_dists),
+            cand_ids.shape[1], degree, rng_factor, 1 if fill_pruned else 0,
+            p(out))
+        if rc != 0:
+            raise SptagAmdError(rc, "rng_prune")
+        return out
+
     def Add(self, vectors, normalized=False):
         """Online add (reference AddIndex semantics below the tree-rebuild
         threshold); runs GPU refine searches per added vector."""
@@ -450,6 +489,25 @@ def group_knn_device(d_vectors_ptr, valuetype, distmethod, n, dim,
         ctypes.c_void_p(d_vids_ptr), ctypes.c_void_p(d_dists_ptr))
     if rc != 0:
         raise SptagAmdError(rc, "group_knn_device")
+
+
+def rng_prune_device(d_vectors_ptr, valuetype, distmethod, n, dim,
+                     d_nodes_ptr, nrows, d_cand_ids_ptr, d_cand_dists_ptr,
+                     ncand, degree, rng_factor, fill_pruned, d_out_ptr,
+                     device=0):
+    """AnnIndex.RngPrune without a handle, on HIP device addresses (e.g. torch
+    tensors' .data_ptr()): vectors [n, dim] of `valuetype`, int32 nodes
+    [nrows], int32 / float32 lists [nrows, ncand], output int32
+    [nrows, degree]. The caller guarantees that every node and every
+    candidate id >= 0 is inside [0, n)."""
+    dm = {"L2": DM_L2, "Cosine": DM_COSINE}.get(distmethod, distmethod)
+    rc = load_library().sptag_amd_rng_prune_device(
+        device, ctypes.c_void_p(d_vectors_ptr), valuetype, dm, n, dim,
+        ctypes.c_void_p(d_nodes_ptr), nrows, ctypes.c_void_p(d_cand_ids_ptr),
+        ctypes.c_void_p(d_cand_dists_ptr), ncand, degree, rng_factor,
+        1 if fill_pruned else 0, ctypes.c_void_p(d_out_ptr))
+    if rc != 0:
+        raise SptagAmdError(rc, "rng_prune_device")
 
 
 def merge_topk(vids, dists, vid_base, k, device=0):

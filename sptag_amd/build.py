@@ -599,17 +599,66 @@ def _rng_prune(xf, cid, cdd, degree, rng_factor, fill_pruned=False):
     return out
 
 
+def _rng_prune_hip(xf, cid, cdd, degree, rng_factor, fill_pruned=False,
+                   nodes=None):
+    """_rng_prune by the RNG-prune HIP kernels (sptag_amd.rng_prune_device):
+    the same rule on the same lists, with the search path's f32 L2 distances
+    between candidates in place of the |a|^2 + |b|^2 - 2ab identity, at most
+    degree x C of them per row, and no [B, C, C] tensor, so any number of
+    rows goes in one call. nodes: the rows' own vector ids, which the kernel
+    skips in the lists (None: nothing to skip, as for pools that went through
+    _merge_candidates)."""
+    if xf.device.type != "cuda":
+        raise RuntimeError('prune="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
+    from . import rng_prune_device, VT_FLOAT, DM_L2
+    n, d = xf.shape
+    rows, C = cid.shape
+    xf = xf.contiguous()
+    cid = cid.to(torch.int32).contiguous()
+    cdd = cdd.to(torch.float32).contiguous()
+    if nodes is None:
+        nodes = torch.full((rows,), -1, dtype=torch.int32, device=xf.device)
+    nodes = nodes.to(torch.int32).contiguous()
+    out = torch.empty((rows, degree), dtype=torch.int32, device=xf.device)
+    if rows == 0:
+        return out
+    torch.cuda.synchronize(xf.device)     # the library runs on the default stream
+    rng_prune_device(xf.data_ptr(), VT_FLOAT, DM_L2, n, d, nodes.data_ptr(),
+                     rows, cid.data_ptr(), cdd.data_ptr(), C, degree,
+                     rng_factor, fill_pruned, out.data_ptr(),
+                     device=xf.device.index or 0)
+    return out
+
+
+def _prune_fn(prune):
+    """the prune step by name: f(xf, cid, cdd, degree, rng_factor,
+    fill_pruned=False, nodes=None)"""
+    if prune == "torch":
+        return lambda xf, cid, cdd, degree, rng_factor, fill_pruned=False, \
+            nodes=None: _rng_prune(xf, cid, cdd, degree, rng_factor, fill_pruned)
+    if prune == "hip":
+        return _rng_prune_hip
+    raise ValueError(f'prune must be "torch" or "hip", got {prune!r}')
+
+
 def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
                     rng_factor=1.0, seed=2016, device=None, point_chunk=None,
-                    verbose=False, leaf_knn="torch"):
+                    verbose=False, leaf_knn="torch", prune="torch"):
     """Returns (graph, cand_ids, cand_dst), tensors on the device: graph
     int32 [n, degree] (RNG-pruned, ascending, -1 padded) and the [n, cand]
     candidate pools it was pruned from, which the refine steps grow.
     leaf_knn: "torch" (padded GEMM + topk) or "hip" (the grouped-kNN
-    kernels; GPU only) for the exact KNN inside the TP-tree leaves."""
+    kernels; GPU only) for the exact KNN inside the TP-tree leaves.
+    prune: "torch" (_rng_prune) or "hip" (the RNG-prune kernels; GPU only)
+    for the RebuildNeighbors step."""
     if leaf_knn not in _LEAF_KNN:
         raise ValueError(f'leaf_knn must be "torch" or "hip", got {leaf_knn!r}')
+    prune_fn = _prune_fn(prune)
     device, xf, gen = _prologue(vectors, device, seed + 77)
+    if prune == "hip" and xf.device.type != "cuda":
+        raise RuntimeError('prune="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
     n = xf.shape[0]
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
 
@@ -632,7 +681,12 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
     if point_chunk is None:
         # the width _rng_prune will see, so that it never splits a chunk
         wide = cand + (0 if bridge_ids is None else bridge_ids.shape[1])
-        point_chunk = _prune_chunk(wide, xf.shape[1])
+        if prune == "hip":
+            # no [B, C, C] tensor: the merge's transients and the bridges'
+            # [B, 8, d] gathers bound the chunk
+            point_chunk = max(4096, int(2e9 // (wide * 24 + 64 * xf.shape[1])))
+        else:
+            point_chunk = _prune_chunk(wide, xf.shape[1])
     graph = torch.full((n, degree), -1, dtype=torch.int32, device=device)
     for s, e in _chunks(n, point_chunk):
         cid, cdd = ids[s:e], dst[s:e]
@@ -643,7 +697,8 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
             cid, cdd = _merge_candidates(cid, cdd, bi, bd,
                                          cid.shape[1] + bi.shape[1],
                                          self_ids[s:e])
-        graph[s:e] = _rng_prune(xf, cid, cdd, degree, rng_factor)
+        graph[s:e] = prune_fn(xf, cid, cdd, degree, rng_factor,
+                              nodes=self_ids[s:e])
         if verbose and (s // point_chunk) % 20 == 0:
             print(f"  rng prune {e}/{n}")
     return graph, ids, dst
@@ -651,7 +706,7 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
 
 def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
                  rounds=2, hop_sample=8, rng_factor=1.0, device=None,
-                 point_chunk=None, seed=2016, verbose=False):
+                 point_chunk=None, seed=2016, verbose=False, prune="torch"):
     """Neighborhood refinement: the reference refines each node's edges from
     a CEF-sized candidate pool gathered by searching the index itself
     (NeighborhoodGraph.h:460-560 RefineGraph/RefineNode). Here the pool is
@@ -659,8 +714,13 @@ def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
     reverse edges — then RNG-pruned with the same RebuildNeighbors rule.
     Returns (graph int32 [n, degree], cand_ids, cand_dst), all tensors on
     the device (the graph used to come back as a numpy array); a graph
-    tensor already on the device, and the pools, are updated in place."""
+    tensor already on the device, and the pools, are updated in place.
+    prune: as in build_rng_graph; the chunking is the same for both."""
+    prune_fn = _prune_fn(prune)
     device, xf, _ = _prologue(vectors, device, seed + 123)
+    if prune == "hip" and xf.device.type != "cuda":
+        raise RuntimeError('prune="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
     n = xf.shape[0]
     g = torch.as_tensor(graph, device=device)
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
@@ -694,8 +754,8 @@ def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
             newd = _exact_l2(xf, torch.arange(s, e, device=device), newc)
             cand_ids[s:e], cand_dst[s:e] = _merge_candidates(
                 cand_ids[s:e], cand_dst[s:e], newc, newd, cand, self_ids[s:e])
-            g[s:e] = _rng_prune(xf, cand_ids[s:e], cand_dst[s:e], degree,
-                                rng_factor)
+            g[s:e] = prune_fn(xf, cand_ids[s:e], cand_dst[s:e], degree,
+                              rng_factor, nodes=self_ids[s:e])
         if verbose:
             print(f"  refine round {r + 1}/{rounds} done")
     return g, cand_ids, cand_dst
@@ -715,7 +775,7 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
                       cand_dst, distmethod, *, algo="BKT", degree=32,
                       cand=256, rounds=1, k=512, max_check=8192,
                       rng_factor=1.0, chunk=0, fill_pruned=False,
-                      verbose=False):
+                      verbose=False, prune="torch"):
     """The reference's own refinement recipe (NeighborhoodGraph.h:460-560
     RefineGraph: every node re-searches the CURRENT index and its edges are
     RNG-rebuilt from the results) — run on the PRODUCT GPU searcher via the
@@ -727,8 +787,9 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
     searcher has no CPU path); vectors_t is the normalized torch tensor on
     the device; graph is a tensor on that device; cand lists are the
     builder's pools (merged in). All three are updated in place and
-    returned."""
+    returned. prune: as in build_rng_graph."""
     import sptag_amd
+    prune_fn = _prune_fn(prune)
     device = vectors_t.device
     n = vectors_t.shape[0]
     xf = vectors_t if vectors_t.dtype == torch.float32 else vectors_t.float()
@@ -788,8 +849,9 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
             wide = cand + sv_s.shape[1]
             wi, wd = _merge_candidates(cand_ids[s0:e0], cand_dst[s0:e0],
                                        sv_s, sd_s, wide, self_ids[s0:e0])
-            graph[s0:e0] = _rng_prune(xf, wi, wd, degree, rng_factor,
-                                      fill_pruned=fill_pruned)
+            graph[s0:e0] = prune_fn(xf, wi, wd, degree, rng_factor,
+                                    fill_pruned=fill_pruned,
+                                    nodes=self_ids[s0:e0])
             cand_ids[s0:e0] = wi[:, :cand]
             cand_dst[s0:e0] = wd[:, :cand]
             del wi, wd
@@ -807,10 +869,12 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
                        refine_rounds=0, search_refine_rounds=0, kdt_trees=1,
                        srefine_k=512, srefine_mc=8192, fill_pruned=False,
                        seed=2016, device=None, normalized=False,
-                       verbose=False, leaf_knn="torch"):
+                       verbose=False, leaf_knn="torch", prune="torch"):
     """Full build: returns dict(vectors, tree_start, tree_nodes, graph) ready
     for AnnIndex.FromArrays (vectors already cosine-normalized when needed,
-    as the reference stores them on disk)."""
+    as the reference stores them on disk). prune: "torch" or "hip" (GPU
+    only), the RebuildNeighbors step of every graph stage."""
+    _prune_fn(prune)
     if not normalized:
         vectors = normalize_base(vectors, distmethod)
     if algo == "KDT":
@@ -824,18 +888,20 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
         print(f"  {algo} tree: {len(tree_nodes)} nodes")
     graph, cids, cdst = build_rng_graph(
         vectors, degree=degree, ntrees=ntrees, tpt_leaf=tpt_leaf, cand=cand,
-        seed=seed, device=device, verbose=verbose, leaf_knn=leaf_knn)
+        seed=seed, device=device, verbose=verbose, leaf_knn=leaf_knn,
+        prune=prune)
     if refine_rounds > 0:
         graph, cids, cdst = refine_graph(
             vectors, graph, cids, cdst, degree=degree, cand=cand,
-            rounds=refine_rounds, device=device, seed=seed, verbose=verbose)
+            rounds=refine_rounds, device=device, seed=seed, verbose=verbose,
+            prune=prune)
     if search_refine_rounds > 0 and torch.cuda.is_available():
         xt = torch.as_tensor(vectors, device=device or _dev())
         graph, cids, cdst = refine_via_search(
             xt, tree_start, tree_nodes, graph, cids, cdst, distmethod,
             algo=algo, degree=degree, cand=cand, k=srefine_k,
             max_check=srefine_mc, fill_pruned=fill_pruned,
-            rounds=search_refine_rounds, verbose=verbose)
+            rounds=search_refine_rounds, verbose=verbose, prune=prune)
         del xt
     return {"vectors": vectors, "tree_start": tree_start,
             "tree_nodes": tree_nodes, "graph": graph.cpu().numpy(),

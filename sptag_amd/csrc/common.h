@@ -216,6 +216,20 @@ int launch_group_knn(int valuetype, int distmethod, const void* vectors, int32_t
                      int32_t dim, const int32_t* members, const GroupTile* tiles,
                      int32_t ntiles, int32_t k, int32_t* out_v, float* out_d);
 
+/* RNG prune (exact.hip): RebuildNeighbors over candidate lists. Row r walks
+ * cand_ids[r][0..ncand) (ascending cand_dists, never recomputed) in order
+ * while fewer than `degree` are accepted; a candidate with id < 0, id ==
+ * nodes[r] or a non-finite distance is skipped, one for which an accepted a
+ * has rng_factor * dist(a, c) < cand_dists[c] is rejected, any other is
+ * accepted. out[r] receives the accepted ids in list order, with fill_pruned
+ * and a short row its first degree - count valid rejected candidates among
+ * them, then -1. 1 <= ncand <= 1024, 1 <= degree <= MAX_DEG. All pointers are
+ * device memory; every id >= 0 is inside the vectors. */
+int launch_rng_prune(int valuetype, int distmethod, const void* vectors, int32_t dim,
+                     const int32_t* nodes, int32_t nrows, const int32_t* cand_ids,
+                     const float* cand_dists, int32_t ncand, int32_t degree,
+                     float rng_factor, int32_t fill_pruned, int32_t* out);
+
 /* heap probe (tests/test_gpu_heap_ops.py): a script of nops heap operations
  * (ops[i] != 0: insert {nodes[i], dists[i]}; 0: pop) on a heap of capacity
  * `cap` whose entries [0..lsplit] sit in LDS (lsplit 0: none), run once with

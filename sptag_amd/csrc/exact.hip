@@ -1087,6 +1087,510 @@ void group_i8_kernel(const int8_t* __restrict__ vectors, int d,
 }
 
 /* ------------------------------------------------------------------ *
+ * RNG prune: RebuildNeighbors over candidate lists
+ * ------------------------------------------------------------------ *
+ * Row r has a node id and a list of C candidates in ascending distance. The
+ * list is walked in order while fewer than `degree` are accepted; a valid
+ * candidate c (id >= 0, not the node, finite distance) is rejected when some
+ * accepted a has factor * dist(a, c) < cand_dists[c], and accepted otherwise.
+ * The rule needs dist(accepted, candidate) only, so nothing like the C x C
+ * matrix is formed: a workgroup owns one row, keeps the accepted vectors in
+ * LDS as the "query tile" of the kernels above (32 slots, or 64 for
+ * degree > 32) and streams the list as row tiles, each candidate vector
+ * gathered from global memory once.
+ *
+ *   tile    A tile is speculative: which of its candidates are accepted is
+ *           not known when its distances are computed. So a tile computes
+ *           dist(accepted before the tile, tile) and dist(tile, tile), as
+ *           bits: rej[c] (some earlier accepted vector rejects c) and
+ *           viol[c] (bit q: candidate q of the tile would reject c). One wave
+ *           then walks the tile in list order: c is accepted iff it is valid,
+ *           rej[c] is clear and viol[c] has no bit of a candidate accepted
+ *           earlier in this walk. That is the serial rule exactly: every
+ *           pair the rule would look at has been compared with the same
+ *           operands, and pairs it would not look at are masked out.
+ *   append  The vectors of the newly accepted candidates are copied to their
+ *           slots of the query tile from the tile's copy in LDS.
+ *   stop    A row ends at `degree` accepted; later tiles are never loaded.
+ *   lists   The ids and distances of the whole list (C <= 1024) are read
+ *           into LDS first, so no vector load ever waits for its id.
+ *   fill    With fill_pruned, a row that ends short keeps its first
+ *           degree - count valid rejected candidates too; the kept ids go
+ *           out in list order (a status byte per candidate, ballots).
+ *
+ * f32: 256 threads, tiles of 16 candidates, the micro-tiles and the
+ *   reference-order fold of the kernels above. RES: vectors whole in LDS, the next
+ *   tile's loads in flight in registers during the math. Otherwise (large
+ *   dims) the accepted vectors and the tile stream through LDS in slabs of
+ *   FKS columns with the accumulators kept; the accepted vectors are then
+ *   read again (by id) for every tile, the candidates still once.
+ * int8: one wave, tiles of 32 candidates, three 32x32 MFMA blocks a tile
+ *   (accepted 0..31, accepted 32..63, tile x tile), everything resident. */
+
+enum { RP_INVALID = 0, RP_VALID = 1, RP_ACC = 2, RP_REJ = 3 };
+enum { RP_MAX_C = 1024, RP_LDS_MAX = 65536, RI_T = 32, RI_NP = (I_MAX_W + 1) / 2 };
+
+struct RpCtl {
+    int count;              /* accepted so far */
+    uint32_t newmask;       /* accepted candidates of the last tile */
+    uint32_t rej;           /* f32: bit c, an earlier accepted vector rejects c */
+    uint32_t viol[32];      /* f32: bit q of [c], tile candidate q rejects c */
+    int32_t accid[MAX_DEG]; /* accepted ids, in list order */
+    int asd[MAX_DEG];       /* int8: self-dots of the accepted vectors */
+    int tsd[RI_T];          /* int8: and of the tile's */
+};
+
+struct RpLds { uint32_t ctl, acc, tile, cids, cdd, status, total; };
+
+/* acc_words / tile_words: dwords of the accepted vectors and of a tile */
+static inline __host__ __device__ RpLds rp_lds(uint32_t acc_words, uint32_t tile_words, int C)
+{
+    RpLds l;
+    uint32_t b = 0;
+    l.ctl = b;    b += (uint32_t)(sizeof(RpCtl) + 15) & ~15u;
+    l.acc = b;    b += acc_words * 4;
+    l.tile = b;   b += tile_words * 4;
+    l.cids = b;   b += (uint32_t)C * 4;
+    l.cdd = b;    b += (uint32_t)C * 4;
+    l.status = b; b += ((uint32_t)C + 3) & ~3u;
+    l.total = b;
+    return l;
+}
+
+/* whether the f32 kernel keeps nqt * 32 accepted vectors and a tile whole */
+static inline __host__ __device__ bool rp_f32_resident(int d, int nqt, int C)
+{
+    const int qs = f32_qstride(d);
+    return qs <= FQRES_MAX &&
+           rp_lds((uint32_t)(nqt * XQT * qs), (uint32_t)(FRT * qs), C).total <= RP_LDS_MAX;
+}
+
+/* the row's list into LDS, every candidate's status, an empty accepted set.
+ * Ends with a barrier. */
+DEV void rp_lists(RpCtl* ctl, int32_t* cids, float* cdd, uint8_t* status,
+                  const int32_t* __restrict__ gi, const float* __restrict__ gd, int C,
+                  int32_t node)
+{
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const int32_t id = gi[c];
+        const float dd = gd[c];
+        cids[c] = id;
+        cdd[c] = dd;
+        status[c] = (id >= 0 && id != node && __builtin_isfinite(dd)) ? RP_VALID : RP_INVALID;
+    }
+    if (threadIdx.x == 0) { ctl->count = 0; ctl->newmask = 0; ctl->rej = 0; }
+    if (threadIdx.x < 32) ctl->viol[threadIdx.x] = 0;
+    __syncthreads();
+}
+
+/* One wave walks a tile of nt candidates in list order. Lane c holds viol[c];
+ * bit c of okmask: c is valid and no earlier accepted vector rejects it. cnt
+ * (wave-uniform) goes from the accepted count before the tile to the one
+ * after it; returns the accepted candidates. */
+DEV uint32_t rp_resolve(uint32_t viol, uint32_t okmask, int nt, int& cnt, int degree)
+{
+    uint32_t accm = 0;
+    for (int c = 0; c < nt && cnt < degree; c++) {
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)viol, c);
+        if (((okmask >> c) & 1) && !(v & accm)) {
+            accm |= 1u << c;
+            cnt++;
+        }
+    }
+    return accm;
+}
+
+/* the walk's outcome into LDS: lane < nt is candidate c of the list */
+DEV void rp_commit(RpCtl* ctl, uint8_t* status, const int32_t* cids, int c, bool valid,
+                   int lane, uint32_t accm, int count0, int cnt)
+{
+    if (valid) {
+        const bool a = (accm >> lane) & 1;
+        status[c] = a ? RP_ACC : RP_REJ;
+        if (a) ctl->accid[count0 + __popc(accm & ((1u << lane) - 1))] = cids[c];
+    }
+    if (lane == 0) { ctl->count = cnt; ctl->newmask = accm; }
+}
+
+/* One wave writes the row: the accepted ids, with `fill` and a short row the
+ * first degree - count rejected ones among them, in list order; then -1. */
+DEV void rp_write_out(const RpCtl* ctl, const uint8_t* status, const int32_t* cids, int C,
+                      int degree, int fill, int32_t* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int cnt = ctl->count;
+    if (!fill || cnt >= degree) {
+        for (int i = lane; i < degree; i += 64) out[i] = i < cnt ? ctl->accid[i] : -1;
+        return;
+    }
+    const uint64_t below = (1ull << lane) - 1;
+    const int spare = degree - cnt;
+    int pos = 0, rejseen = 0;
+    for (int base = 0; base < C; base += 64) {
+        const int c = base + lane;
+        const int st = c < C ? status[c] : RP_INVALID;
+        const bool isrej = st == RP_REJ || st == RP_VALID;
+        const uint64_t rb = __ballot(isrej);
+        const bool keep = st == RP_ACC || (isrej && rejseen + __popcll(rb & below) < spare);
+        const uint64_t kb = __ballot(keep);
+        if (keep) out[pos + __popcll(kb & below)] = cids[c];
+        pos += __popcll(kb);
+        rejseen += __popcll(rb);
+    }
+    for (int i = pos + lane; i < degree; i += 64) out[i] = -1;
+}
+
+/* columns c .. c+3 of the row of d floats at `row`, zero past d and for a
+ * null row (f32_cols_load with the column given) */
+DEV float4 rp_cols4(const float* __restrict__ row, int d, int c, bool vec)
+{
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (row && c < d) {
+        const float* p = row + c;
+        if (vec) {
+            v = *(const float4*)p;
+        } else {
+            v.x = p[0];
+            if (c + 1 < d) v.y = p[1];
+            if (c + 2 < d) v.z = p[2];
+            if (c + 3 < d) v.w = p[3];
+        }
+    }
+    return v;
+}
+
+/* f32_slab_math / f32_fold over the first NI query rows of the micro-tile
+ * (queries gq + 4*i, i < NI), with a row stride of its own for the rows */
+template <int DM, int NI>
+DEV void rp_math(float (&acc)[FMQ][FMR], const float* qb, const float* rb, int qstride,
+                 int rstride, int slab, int d, int g)
+{
+    if (slab == 0) {
+#pragma unroll
+        for (int i = 0; i < NI; i++)
+#pragma unroll
+            for (int j = 0; j < FMR; j++) acc[i][j] = 0.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < FKS / 16; c++) {
+        if (slab * FKS + c * 16 + 16 > d) break;
+        float x[NI], y[FMR];
+#pragma unroll
+        for (int i = 0; i < NI; i++) x[i] = qb[4 * i * qstride + c * 16 + g];
+#pragma unroll
+        for (int j = 0; j < FMR; j++) y[j] = rb[j * rstride + c * 16 + g];
+#pragma unroll
+        for (int i = 0; i < NI; i++)
+#pragma unroll
+            for (int j = 0; j < FMR; j++) acc[i][j] = xstep<DM>(x[i], y[j], acc[i][j]);
+    }
+}
+
+template <int DM, int NI>
+DEV void rp_fold(const float (&acc)[FMQ][FMR], const float* qb, const float* rb, int qstride,
+                 int rstride, int slab, int d, int g, float (&dist)[FMQ])
+{
+    const int nd16 = d & ~15, nd8 = d & ~7, nd4 = d & ~3;
+    const int tc = nd16 - slab * FKS;
+    float x8[NI], x4[NI], y8[FMR], y4[FMR];
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+        x8[i] = (nd8 > nd16 && g < 8) ? qb[4 * i * qstride + tc + g] : 0.0f;
+        x4[i] = (nd4 > nd8 && g < 4) ? qb[4 * i * qstride + tc + (nd8 - nd16) + g] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < FMR; j++) {
+        y8[j] = (nd8 > nd16 && g < 8) ? rb[j * rstride + tc + g] : 0.0f;
+        y4[j] = (nd4 > nd8 && g < 4) ? rb[j * rstride + tc + (nd8 - nd16) + g] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+        float mine = 0.0f;
+#pragma unroll
+        for (int j = 0; j < FMR; j++) {
+            float a = acc[i][j];
+            a = a + dpp<DPP_ROW_SHL8>(a);
+            if (nd8 > nd16) a = xstep<DM>(x8[i], y8[j], a);
+            a = a + dpp<DPP_ROW_SHL4>(a);
+            if (nd4 > nd8) a = xstep<DM>(x4[i], y4[j], a);
+            const float s = ((dpp<DPP_QUAD0>(a) + dpp<DPP_QUAD1>(a)) +
+                             dpp<DPP_QUAD2>(a)) + dpp<DPP_QUAD3>(a);
+            mine = (j == 0 || g == j) ? s : mine;
+        }
+        for (int c = nd4; c < d; c++)
+            mine = xstep<DM>(qb[4 * i * qstride + (c - slab * FKS)],
+                             rb[(g & 3) * rstride + (c - slab * FKS)], mine);
+        dist[i] = (DM == DM_L2) ? mine : 1.0f - mine;
+    }
+}
+
+/* NQT: query tiles of 32 accepted slots (2 for degree > 32) */
+template <int DM, bool RES, int NQT>
+__global__ __launch_bounds__(XTHREADS, NQT == 1 ? 2 : 1)
+void rng_prune_f32_kernel(const float* __restrict__ vectors, int d,
+                          const int32_t* __restrict__ nodes,
+                          const int32_t* __restrict__ cand_ids,
+                          const float* __restrict__ cand_dists, int C, int degree,
+                          float factor, int fill, int32_t* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const int qs = RES ? f32_qstride(d) : FQSS;    /* row stride of both buffers */
+    const RpLds L = rp_lds((uint32_t)(NQT * XQT * qs), (uint32_t)(FRT * qs), C);
+    RpCtl* ctl = (RpCtl*)(xlds + L.ctl);
+    float* abuf = (float*)(xlds + L.acc);       /* accepted vectors (or their slab) */
+    float* tbuf = (float*)(xlds + L.tile);      /* the tile's (or their slab) */
+    int32_t* cids = (int32_t*)(xlds + L.cids);
+    float* cdd = (float*)(xlds + L.cdd);
+    uint8_t* status = xlds + L.status;
+    const int tid = threadIdx.x;
+    const int g = tid & 15, gq = (tid >> 4) & 3, gr = tid >> 6, lr = tid >> 4;
+    const size_t row = blockIdx.x;
+    rp_lists(ctl, cids, cdd, status, cand_ids + row * C, cand_dists + row * C, C, nodes[row]);
+
+    const bool vec = (d & 3) == 0 && ((uintptr_t)vectors & 15) == 0;
+    const int nslab = (d + FKS - 1) / FKS;
+    const int ntile = (C + FRT - 1) / FRT;
+    /* the vector of candidate lr of tile t, null for a hole or past the list */
+    auto cand_row = [&](int t) -> const float* {
+        const int c = t * FRT + lr;
+        const int32_t id = c < C ? cids[c] : -1;
+        return id >= 0 ? vectors + (size_t)id * d : nullptr;
+    };
+    /* RES: this thread's columns 4*(g + 16*k) of row lr of a tile */
+    float4 pre[FQRES_MAX / 64];
+    auto tile_load = [&](int t) {
+        const float* p = cand_row(t);
+#pragma unroll
+        for (int k = 0; k < FQRES_MAX / 64; k++) {
+            const int col = 4 * (g + 16 * k);
+            if (col < qs) pre[k] = rp_cols4(p, d, col, vec);
+        }
+    };
+    auto tile_store = [&]() {
+#pragma unroll
+        for (int k = 0; k < FQRES_MAX / 64; k++) {
+            const int col = 4 * (g + 16 * k);
+            if (col < qs) *(float4*)(tbuf + lr * qs + col) = pre[k];
+        }
+    };
+    if constexpr (RES) {
+        tile_load(0);
+        tile_store();
+        __syncthreads();
+    }
+
+    float a0[FMQ][FMR], a1[FMQ][FMR], aT[FMQ][FMR];
+    for (int t = 0;; t++) {
+        const int count0 = __builtin_amdgcn_readfirstlane(ctl->count);
+        const bool use0 = count0 > 0, use1 = NQT == 2 && count0 > XQT;   /* tiles in use */
+        if constexpr (RES) {
+            if (t + 1 < ntile) tile_load(t + 1);    /* in flight while this tile computes */
+        }
+        for (int slab = 0; slab < nslab; slab++) {
+            const int off = RES ? slab * FKS : 0;
+            if constexpr (!RES) {
+                for (int r16 = 0; r16 < NQT * XQT && r16 < count0; r16 += 16) {
+                    const int slot = r16 + lr;
+                    const int32_t id = slot < count0 ? ctl->accid[slot] : -1;
+                    f32_slab_store(abuf, FQSS,
+                                   f32_cols_load(id >= 0 ? vectors + (size_t)id * d : nullptr,
+                                                 d, slab * FKS, vec), r16);
+                }
+                f32_slab_store(tbuf, FQSS, f32_cols_load(cand_row(t), d, slab * FKS, vec));
+                __syncthreads();
+            }
+            const float* qa = abuf + gq * qs + off;         /* accepted gq + 4*i */
+            const float* qt = tbuf + gq * qs + off;         /* tile candidate gq + 4*i */
+            const float* rb = tbuf + gr * FMR * qs + off;   /* this wave's four candidates */
+            if (use0) rp_math<DM, FMQ>(a0, qa, rb, qs, qs, slab, d, g);
+            if (use1) rp_math<DM, FMQ>(a1, qa + XQT * qs, rb, qs, qs, slab, d, g);
+            rp_math<DM, 4>(aT, qt, rb, qs, qs, slab, d, g);
+
+            if (slab == nslab - 1) {
+                float d0[FMQ] = {}, d1[FMQ] = {}, dT[FMQ] = {};
+                if (use0) rp_fold<DM, FMQ>(a0, qa, rb, qs, qs, slab, d, g, d0);
+                if (use1) rp_fold<DM, FMQ>(a1, qa + XQT * qs, rb, qs, qs, slab, d, g, d1);
+                rp_fold<DM, 4>(aT, qt, rb, qs, qs, slab, d, g, dT);
+                /* lane g < FMR of a group: candidate r of the tile against
+                 * accepted gq + 4*i (+ 32) and tile candidates gq + 4*i */
+                const int r = gr * FMR + (g & 3), c = t * FRT + r;
+                if (g < FMR && c < C) {
+                    const float cdr = cdd[c];
+                    bool rej = false;
+                    uint32_t m = 0;
+#pragma unroll
+                    for (int i = 0; i < FMQ; i++) {
+                        if (gq + 4 * i < count0 && factor * d0[i] < cdr) rej = true;
+                        if (NQT == 2 && XQT + gq + 4 * i < count0 && factor * d1[i] < cdr)
+                            rej = true;
+                        if (i < 4 && factor * dT[i] < cdr) m |= 1u << (gq + 4 * i);
+                    }
+                    if (rej) atomicOr(&ctl->rej, 1u << r);
+                    if (m) atomicOr(&ctl->viol[r], m);
+                }
+            }
+            if constexpr (!RES) __syncthreads();    /* the slab is free */
+        }
+        __syncthreads();
+        if (gr == 0) {
+            const int c = t * FRT + tid;
+            const bool valid = tid < FRT && c < C && status[c] == RP_VALID;
+            const uint32_t viol = tid < FRT ? ctl->viol[tid] : 0u;
+            const uint32_t ok = (uint32_t)__ballot(valid) &
+                                ~(uint32_t)__builtin_amdgcn_readfirstlane((int)ctl->rej);
+            int cnt = count0;
+            const uint32_t accm = rp_resolve(viol, ok, FRT, cnt, degree);
+            rp_commit(ctl, status, cids, c, valid, tid, accm, count0, cnt);
+            if (tid == 0) ctl->rej = 0;
+            if (tid < FRT) ctl->viol[tid] = 0;
+        }
+        __syncthreads();
+        const uint32_t newmask = (uint32_t)__builtin_amdgcn_readfirstlane((int)ctl->newmask);
+        if constexpr (RES) {        /* the accepted vectors to their slots */
+            if ((newmask >> lr) & 1) {
+                const int slot = count0 + __popc(newmask & ((1u << lr) - 1));
+#pragma unroll
+                for (int k = 0; k < FQRES_MAX / 64; k++) {
+                    const int col = 4 * (g + 16 * k);
+                    if (col < qs)
+                        *(float4*)(abuf + slot * qs + col) = *(const float4*)(tbuf + lr * qs + col);
+                }
+            }
+        }
+        if (__builtin_amdgcn_readfirstlane(ctl->count) >= degree || t + 1 == ntile) break;
+        __syncthreads();
+        if constexpr (RES) {
+            tile_store();
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (gr == 0) rp_write_out(ctl, status, cids, C, degree, fill, out + row * degree);
+}
+
+template <int DM>
+__global__ __launch_bounds__(64)
+void rng_prune_i8_kernel(const int8_t* __restrict__ vectors, int d,
+                         const int32_t* __restrict__ nodes,
+                         const int32_t* __restrict__ cand_ids,
+                         const float* __restrict__ cand_dists, int C, int degree,
+                         float factor, int fill, int32_t* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const int W = (d + 3) >> 2, WL = W | 1;
+    const RpLds L = rp_lds((uint32_t)(MAX_DEG * WL), (uint32_t)(RI_T * WL), C);
+    RpCtl* ctl = (RpCtl*)(xlds + L.ctl);
+    uint32_t* abuf = (uint32_t*)(xlds + L.acc);     /* [MAX_DEG][WL] accepted vectors */
+    uint32_t* tbuf = (uint32_t*)(xlds + L.tile);    /* [RI_T][WL] the tile's */
+    int32_t* cids = (int32_t*)(xlds + L.cids);
+    float* cdd = (float*)(xlds + L.cdd);
+    uint8_t* status = xlds + L.status;
+    const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
+    const size_t row = blockIdx.x;
+    rp_lists(ctl, cids, cdd, status, cand_ids + row * C, cand_dists + row * C, C, nodes[row]);
+
+    /* whole dwords to a row, dword aligned: lanes 2r and 2r + 1 load the even
+     * and the odd dwords of candidate r into registers a tile ahead; other
+     * pitches are packed from bytes at the store */
+    const bool wide = (d & 3) == 0 && ((uintptr_t)vectors & 3) == 0;
+    const int ntile = (C + RI_T - 1) / RI_T;
+    uint32_t pre[RI_NP];
+    auto tile_load = [&](int t) {
+        if (!wide) return;
+        const int c = t * RI_T + (lane >> 1);
+        const int32_t id = c < C ? cids[c] : -1;
+        const uint32_t* p = (const uint32_t*)(vectors + (size_t)(id >= 0 ? id : 0) * d);
+#pragma unroll
+        for (int j = 0; j < RI_NP; j++) {
+            const int w = (lane & 1) + 2 * j;
+            pre[j] = (id >= 0 && w < W) ? p[w] : 0u;
+        }
+    };
+    /* ends with a barrier behind the tile and its self-dots */
+    auto tile_store = [&](int t) {
+        if (wide) {
+#pragma unroll
+            for (int j = 0; j < RI_NP; j++) {
+                const int w = (lane & 1) + 2 * j;
+                if (w < W) tbuf[(lane >> 1) * WL + w] = pre[j];
+            }
+        } else {
+            for (int i = lane; i < RI_T * W; i += 64) {
+                const int r = i / W, w = i - r * W, c = t * RI_T + r;
+                const int32_t id = c < C ? cids[c] : -1;
+                tbuf[r * WL + w] = id >= 0 ? i8_pack_dword(vectors, id, w, d) : 0u;
+            }
+        }
+        __syncthreads();
+        if (lane < RI_T) {
+            int s = 0;
+            for (int w = 0; w < W; w++) {
+                const int v = (int)tbuf[lane * WL + w];
+                s = __builtin_amdgcn_sdot4(v, v, s, false);
+            }
+            ctl->tsd[lane] = s;
+        }
+        __syncthreads();
+    };
+    tile_load(0);
+    tile_store(0);
+
+    const uint32_t* trow = tbuf + col * WL;
+    for (int t = 0;; t++) {
+        const int count0 = __builtin_amdgcn_readfirstlane(ctl->count);
+        if (t + 1 < ntile) tile_load(t + 1);    /* in flight while this tile computes */
+
+        /* acc[r] is query 8*(r/4) + 4*h + r%4 against candidate `col` */
+        v16i vT, v0 = {}, v1 = {};
+        int bb, bbx;
+        i8_tile_dots<DM>(trow, trow, W, h, vT, bb);
+        if (count0 > 0) i8_tile_dots<DM>(abuf + col * WL, trow, W, h, v0, bbx);
+        if (count0 > 32) i8_tile_dots<DM>(abuf + (32 + col) * WL, trow, W, h, v1, bbx);
+
+        const int c = t * RI_T + col;
+        const float cdc = c < C ? cdd[c] : 0.0f;
+        uint32_t viol = 0;
+        int rej = 0;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int q = 8 * (r >> 2) + 4 * h + (r & 3);
+            const float dT = (DM == DM_L2) ? (float)(ctl->tsd[q] - 2 * vT[r] + bb)
+                                           : (float)(16129 - vT[r]);
+            if (factor * dT < cdc) viol |= 1u << q;
+            if (q < count0) {
+                const float d0 = (DM == DM_L2) ? (float)(ctl->asd[q] - 2 * v0[r] + bb)
+                                               : (float)(16129 - v0[r]);
+                if (factor * d0 < cdc) rej = 1;
+            }
+            if (32 + q < count0) {
+                const float d1 = (DM == DM_L2) ? (float)(ctl->asd[32 + q] - 2 * v1[r] + bb)
+                                               : (float)(16129 - v1[r]);
+                if (factor * d1 < cdc) rej = 1;
+            }
+        }
+        viol |= (uint32_t)__shfl_xor((int)viol, 32);    /* both halves of the queries */
+        rej |= __shfl_xor(rej, 32);
+        const bool valid = lane < RI_T && c < C && status[c] == RP_VALID;
+        const uint32_t ok = (uint32_t)__ballot(valid && !rej);
+        int cnt = count0;
+        const uint32_t accm = rp_resolve(viol, ok, RI_T, cnt, degree);
+        rp_commit(ctl, status, cids, c, valid, lane, accm, count0, cnt);
+        __syncthreads();
+        int slot = count0;          /* the accepted vectors to their slots */
+        for (uint32_t m = accm; m; m &= m - 1, slot++) {
+            const int b = __builtin_ctz(m);
+            for (int w = lane; w < W; w += 64) abuf[slot * WL + w] = tbuf[b * WL + w];
+            if (lane == 0) ctl->asd[slot] = ctl->tsd[b];
+        }
+        if (cnt >= degree || t + 1 == ntile) break;
+        __syncthreads();
+        tile_store(t + 1);
+    }
+    __syncthreads();
+    rp_write_out(ctl, status, cids, C, degree, fill, out + row * degree);
+}
+
+/* ------------------------------------------------------------------ *
  * launchers
  * ------------------------------------------------------------------ */
 
@@ -1147,6 +1651,46 @@ int launch_group_knn(int vt, int dm, const void* vectors, int32_t n, int32_t dim
         hipLaunchKernelGGL(kernel, grid, block, grp_lds(i8_lds(dim).total, IRT).total,
                            nullptr, (const int8_t*)vectors, dim, members, tiles, k, out_v,
                            out_d);
+    }
+    return (int)hipGetLastError();
+}
+
+int launch_rng_prune(int vt, int dm, const void* vectors, int32_t dim, const int32_t* nodes,
+                     int32_t nrows, const int32_t* cand_ids, const float* cand_dists,
+                     int32_t ncand, int32_t degree, float rng_factor, int32_t fill_pruned,
+                     int32_t* out)
+{
+    /* the kernels index nothing outside these bounds */
+    if (nrows < 1 || dim < 1 || ncand < 1 || ncand > RP_MAX_C || degree < 1 ||
+        degree > MAX_DEG || (vt != VT_FLOAT && vt != VT_INT8) ||
+        (vt == VT_INT8 && dim > 4 * I_MAX_W))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(nrows);
+    if (vt == VT_FLOAT) {
+        const int nqt = degree > XQT ? 2 : 1;
+        const bool res = rp_f32_resident(dim, nqt, ncand);
+        const int qs = res ? f32_qstride(dim) : FQSS;
+        const uint32_t lds =
+            rp_lds((uint32_t)(nqt * XQT * qs), (uint32_t)(FRT * qs), ncand).total;
+        auto pick = [&](auto k11, auto k12, auto k01, auto k02) {
+            return res ? (nqt == 1 ? k11 : k12) : (nqt == 1 ? k01 : k02);
+        };
+        auto kernel = dm == DM_L2
+            ? pick(rng_prune_f32_kernel<DM_L2, true, 1>, rng_prune_f32_kernel<DM_L2, true, 2>,
+                   rng_prune_f32_kernel<DM_L2, false, 1>, rng_prune_f32_kernel<DM_L2, false, 2>)
+            : pick(rng_prune_f32_kernel<DM_COSINE, true, 1>,
+                   rng_prune_f32_kernel<DM_COSINE, true, 2>,
+                   rng_prune_f32_kernel<DM_COSINE, false, 1>,
+                   rng_prune_f32_kernel<DM_COSINE, false, 2>);
+        hipLaunchKernelGGL(kernel, grid, dim3(XTHREADS), lds, nullptr, (const float*)vectors,
+                           dim, nodes, cand_ids, cand_dists, ncand, degree, rng_factor,
+                           fill_pruned, out);
+    } else {
+        const uint32_t wl = (uint32_t)((dim + 3) >> 2) | 1;
+        auto kernel = dm == DM_L2 ? rng_prune_i8_kernel<DM_L2> : rng_prune_i8_kernel<DM_COSINE>;
+        hipLaunchKernelGGL(kernel, grid, dim3(64), rp_lds(MAX_DEG * wl, RI_T * wl, ncand).total,
+                           nullptr, (const int8_t*)vectors, dim, nodes, cand_ids, cand_dists,
+                           ncand, degree, rng_factor, fill_pruned, out);
     }
     return (int)hipGetLastError();
 }

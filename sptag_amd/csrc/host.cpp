@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstring>
 #include <initializer_list>
 #include <memory>
@@ -1059,6 +1060,85 @@ int sptag_amd_group_knn(SptagAmdIndex* ix, const int32_t* members, int32_t nmemb
                         d_members.as<int32_t>(), starts, counts, ngroups, k, out.vids(),
                         out.dists());
     return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, total);
+}
+
+/* what both RNG-prune entries can check from the host */
+static bool rng_prune_args_ok(const void* nodes, int32_t nrows, const void* cand_ids,
+                              const void* cand_dists, int32_t ncand, int32_t degree,
+                              float rng_factor, const void* out)
+{
+    return nodes && cand_ids && cand_dists && out && nrows >= 1 && ncand >= 1 &&
+           ncand <= 1024 && degree >= 1 && degree <= MAX_DEG && std::isfinite(rng_factor) &&
+           rng_factor > 0.0f;
+}
+
+/* RNG prune into a device buffer, arguments checked; `device` is current.
+ * Returns once the output is complete. */
+static int rng_prune_core(const void* d_vectors, int vt, int dm, int32_t dim,
+                          const int32_t* d_nodes, int32_t nrows, const int32_t* d_cand_ids,
+                          const float* d_cand_dists, int32_t ncand, int32_t degree,
+                          float rng_factor, int32_t fill_pruned, int32_t* d_out)
+{
+    int err = launch_rng_prune(vt, dm, d_vectors, dim, d_nodes, nrows, d_cand_ids,
+                               d_cand_dists, ncand, degree, rng_factor, fill_pruned, d_out);
+    if (err != 0) {
+        fprintf(stderr, "sptag_amd: rng prune launch failed %d\n", err);
+        return SPTAG_AMD_ERR_INTERNAL;
+    }
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+int sptag_amd_rng_prune_device(int device, const void* d_vectors, int valuetype,
+                               int distmethod, int32_t n, int32_t dim,
+                               const int32_t* d_nodes, int32_t nrows,
+                               const int32_t* d_cand_ids, const float* d_cand_dists,
+                               int32_t ncand, int32_t degree, float rng_factor,
+                               int32_t fill_pruned, int32_t* d_out_graph)
+{
+    if (!d_vectors || n < 1 || dim < 1 || dim > MAX_DIM ||
+        (valuetype != VT_FLOAT && valuetype != VT_INT8) ||
+        (distmethod != DM_L2 && distmethod != DM_COSINE) ||
+        (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) ||
+        !rng_prune_args_ok(d_nodes, nrows, d_cand_ids, d_cand_dists, ncand, degree,
+                           rng_factor, d_out_graph))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    return rng_prune_core(d_vectors, valuetype, distmethod, dim, d_nodes, nrows, d_cand_ids,
+                          d_cand_dists, ncand, degree, rng_factor, fill_pruned, d_out_graph);
+}
+
+int sptag_amd_rng_prune(SptagAmdIndex* ix, const int32_t* nodes, int32_t nrows,
+                        const int32_t* cand_ids, const float* cand_dists, int32_t ncand,
+                        int32_t degree, float rng_factor, int32_t fill_pruned,
+                        int32_t* out_graph)
+{
+    if (!ix || !rng_prune_args_ok(nodes, nrows, cand_ids, cand_dists, ncand, degree,
+                                  rng_factor, out_graph))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available() || !ix->d_vectors) return SPTAG_AMD_ERR_NOGPU;
+    std::lock_guard<std::mutex> g(ix->lock);
+    const size_t ncells = (size_t)nrows * ncand, nout = (size_t)nrows * degree;
+    for (int32_t r = 0; r < nrows; r++)
+        if (nodes[r] < 0 || nodes[r] >= ix->n) return SPTAG_AMD_ERR_PARAM;
+    for (size_t i = 0; i < ncells; i++)
+        if (cand_ids[i] >= ix->n) return SPTAG_AMD_ERR_PARAM;
+    HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
+
+    DevBuf d_nodes, d_ids, d_dists, d_out;
+    int rc;
+    if ((rc = dev_upload(d_nodes, nodes, (size_t)nrows * 4)) != SPTAG_AMD_OK) return rc;
+    if ((rc = dev_upload(d_ids, cand_ids, ncells * 4)) != SPTAG_AMD_OK) return rc;
+    if ((rc = dev_upload(d_dists, cand_dists, ncells * 4)) != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(d_out.alloc(nout * 4), SPTAG_AMD_ERR_OOM);
+    rc = rng_prune_core(ix->d_vectors.as(), ix->vt, ix->dm, ix->dim, d_nodes.as<int32_t>(),
+                        nrows, d_ids.as<int32_t>(), d_dists.as<float>(), ncand, degree,
+                        rng_factor, fill_pruned, d_out.as<int32_t>());
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(hipMemcpy(out_graph, d_out.as(), nout * 4, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
 }
 
 /* Host-side distance restatements for the add path's edge arithmetic
