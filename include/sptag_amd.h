@@ -217,6 +217,57 @@ int sptag_amd_rng_prune_device(int device, const void* d_vectors, int valuetype,
                                int32_t ncand, int32_t degree, float rng_factor,
                                int32_t fill_pruned, int32_t* d_out_graph);
 
+/* Pool join: grow candidate pools, the index builder's step between the leaf
+ * kNN and the RNG prune. Row r has a node id nodes[r] (its query is that
+ * vector), an old pool pool_ids[r][0..npool) with pool_dists[r][0..npool),
+ * used as given and never recomputed, and new candidates new_ids[r][0..nnew).
+ * With new_dists null the distance of every new candidate to the node's
+ * vector is computed: the search paths' distance for the value type and
+ * metric, bit for bit (f32 in the reference's 16/8/4-accumulator order, 1 -
+ * dot for cosine; int8 exact integers, 16129 - dot for cosine). With
+ * new_dists given those values are used and no vector is read.
+ *   - An entry is invalid if its id is < 0 or equals nodes[r], or its given
+ *     distance is not finite. A given -0.0 counts as 0.0.
+ *   - A new candidate whose id is a valid entry of the old pool is dropped:
+ *     the pool's entry and distance stand, and no vector is read for it.
+ *   - Of several valid entries of one id inside the old pool, or inside the
+ *     new list, the smallest (dist, position) stays.
+ * out_ids[r][0..kout) / out_dists[r][0..kout) receive the kout smallest
+ * remaining entries in ascending (dist, id), distances compared as f32
+ * numbers (cosine ones may be negative), ids as int32; all ids are distinct.
+ * Behind them comes padding of id -1 at +inf, so an output is a valid old pool
+ * of a later call. A row is read completely before it is written: the device
+ * form's outputs may be the old pool's own buffers when kout == npool.
+ * 0 <= npool <= 1024, 0 <= nnew <= 1024, npool + nnew >= 1, 1 <= kout <= 1024,
+ * any nrows >= 1; pool_ids and pool_dists may be null at npool == 0. The
+ * handle form takes host arrays and uses the handle's vectors, value type and
+ * metric; the delete set, the tree and the graph are not consulted (BKT and
+ * KDT handles alike). Computed by the pool-join kernels of exact.hip: a
+ * workgroup owns a row, settles validity and duplicates in LDS before any
+ * distance, reads each surviving new vector once and sorts packed (dist, id)
+ * keys. Returns SPTAG_AMD_ERR_PARAM, with the outputs untouched, for a null
+ * required pointer, nrows < 1, a size out of range or both sizes zero, a null
+ * pool pointer with npool > 0, a node outside [0, n) and an id >= n. */
+int sptag_amd_pool_join(SptagAmdIndex* idx, const int32_t* nodes, int32_t nrows,
+                        const int32_t* pool_ids, const float* pool_dists, int32_t npool,
+                        const int32_t* new_ids, const float* new_dists, int32_t nnew,
+                        int32_t kout, int32_t* out_ids, float* out_dists);
+/* The same without a handle: d_vectors ([n][dim] of valuetype), d_nodes, the
+ * lists and the outputs are HIP device buffers on `device`. It checks what the
+ * host can see (the pointers, nrows, the sizes, value type, metric, 1 <= dim
+ * <= 4096, the int8 dim guard of the create calls) and returns
+ * SPTAG_AMD_ERR_PARAM for those. That every node and every id >= 0 is inside
+ * [0, n) is the CALLER'S to guarantee: with d_new_dists null an id outside
+ * makes the kernels read outside d_vectors. Runs on the default stream and
+ * returns after a device synchronise. */
+int sptag_amd_pool_join_device(int device, const void* d_vectors, int valuetype,
+                               int distmethod, int32_t n, int32_t dim,
+                               const int32_t* d_nodes, int32_t nrows,
+                               const int32_t* d_pool_ids, const float* d_pool_dists,
+                               int32_t npool, const int32_t* d_new_ids,
+                               const float* d_new_dists, int32_t nnew, int32_t kout,
+                               int32_t* d_out_ids, float* d_out_dists);
+
 /* Iterative (streaming) search — mirrors the reference's ResultIterator /
  * SearchIndexIterativeNext protocol (inc/Core/VectorIndex.h:43-49,
  * src/Core/ResultIterator.cpp) over a BATCH of nq per-query iterators whose

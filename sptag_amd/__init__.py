@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "group_knn_device",
-           "rng_prune_device",
+           "rng_prune_device", "pool_join_device",
            "MetadataSet", "load_library", "gpu_available", "SptagAmdError"]
 
 _LIB = None
@@ -99,6 +99,18 @@ def load_library():
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
         ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]
+    lib.sptag_amd_pool_join.restype = ctypes.c_int
+    lib.sptag_amd_pool_join.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.sptag_amd_pool_join_device.restype = ctypes.c_int
+    lib.sptag_amd_pool_join_device.argtypes = [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p]
     lib.sptag_amd_save_index.restype = ctypes.c_int
     lib.sptag_amd_save_index.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     for f in ["num_vectors", "dim", "valuetype", "distmethod", "degree",
@@ -416,6 +428,48 @@ class AnnIndex:
             raise SptagAmdError(rc, "rng_prune")
         return out
 
+    def PoolJoin(self, nodes, pool_ids, pool_dists, new_ids, kout,
+                 new_dists=None):
+        """Grow candidate pools: row r merges its old pool (pool_ids[r] with
+        pool_dists[r], used as given; both may be None) with new_ids[r], whose
+        distances are new_dists[r] or, when that is None, the handle's search
+        distance to vector nodes[r]. Ids < 0, nodes[r] itself and non-finite
+        given distances are dropped, a new id already valid in the pool keeps
+        the pool's entry, repeats keep their smallest distance. Returns
+        (ids int32, dists float32), both [nrows, kout]: the kout smallest in
+        ascending (dist, id), padded with -1 at +inf."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        new_ids = np.ascontiguousarray(new_ids, dtype=np.int32)
+        if pool_ids is None:
+            pool_ids = np.empty((nodes.size, 0), dtype=np.int32)
+            pool_dists = np.empty((nodes.size, 0), dtype=np.float32)
+        pool_ids = np.ascontiguousarray(pool_ids, dtype=np.int32)
+        pool_dists = np.ascontiguousarray(pool_dists, dtype=np.float32)
+        if new_dists is not None:
+            new_dists = np.ascontiguousarray(new_dists, dtype=np.float32)
+        if (nodes.ndim != 1 or pool_ids.ndim != 2 or new_ids.ndim != 2 or
+                pool_ids.shape != pool_dists.shape or
+                pool_ids.shape[0] != nodes.size or
+                new_ids.shape[0] != nodes.size or
+                (new_dists is not None and new_dists.shape != new_ids.shape)):
+            raise ValueError("nodes [nrows], pool_ids and pool_dists "
+                             "[nrows, npool], new_ids (and new_dists) "
+                             "[nrows, nnew] expected")
+        kout = int(kout)
+        ids = np.empty((nodes.size, max(kout, 0)), dtype=np.int32)
+        dists = np.empty(ids.shape, dtype=np.float32)
+        # an empty list goes in as a null pointer
+        p = lambda a: (a.ctypes.data_as(ctypes.c_void_p)
+                       if a is not None and a.size else None)
+        rc = self._lib.sptag_amd_pool_join(
+            self._h, p(nodes), nodes.size, p(pool_ids), p(pool_dists),
+            pool_ids.shape[1], p(new_ids), p(new_dists), new_ids.shape[1],
+            kout, ids.ctypes.data_as(ctypes.c_void_p),
+            dists.ctypes.data_as(ctypes.c_void_p))
+        if rc != 0:
+            raise SptagAmdError(rc, "pool_join")
+        return ids, dists
+
     def Add(self, vectors, normalized=False):
         """Online add (reference AddIndex semantics below the tree-rebuild
         threshold); runs GPU refine searches per added vector."""
@@ -508,6 +562,28 @@ def rng_prune_device(d_vectors_ptr, valuetype, distmethod, n, dim,
         1 if fill_pruned else 0, ctypes.c_void_p(d_out_ptr))
     if rc != 0:
         raise SptagAmdError(rc, "rng_prune_device")
+
+
+def pool_join_device(d_vectors_ptr, valuetype, distmethod, n, dim,
+                     d_nodes_ptr, nrows, d_pool_ids_ptr, d_pool_dists_ptr,
+                     npool, d_new_ids_ptr, d_new_dists_ptr, nnew, kout,
+                     d_out_ids_ptr, d_out_dists_ptr, device=0):
+    """AnnIndex.PoolJoin without a handle, on HIP device addresses (e.g. torch
+    tensors' .data_ptr()): vectors [n, dim] of `valuetype`, int32 nodes
+    [nrows], int32 / float32 pools [nrows, npool] and new lists
+    [nrows, nnew], outputs int32 / float32 [nrows, kout], which may be the
+    pool's own buffers when kout == npool. The pool pointers may be None at
+    npool == 0; d_new_dists_ptr None has the distances computed. The caller
+    guarantees that every node and every id >= 0 is inside [0, n)."""
+    dm = {"L2": DM_L2, "Cosine": DM_COSINE}.get(distmethod, distmethod)
+    vp = lambda a: ctypes.c_void_p(a) if a else None
+    rc = load_library().sptag_amd_pool_join_device(
+        device, vp(d_vectors_ptr), valuetype, dm, n, dim, vp(d_nodes_ptr),
+        nrows, vp(d_pool_ids_ptr), vp(d_pool_dists_ptr), npool,
+        vp(d_new_ids_ptr), vp(d_new_dists_ptr), nnew, kout,
+        vp(d_out_ids_ptr), vp(d_out_dists_ptr))
+    if rc != 0:
+        raise SptagAmdError(rc, "pool_join_device")
 
 
 def merge_topk(vids, dists, vid_base, k, device=0):

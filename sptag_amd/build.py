@@ -500,6 +500,66 @@ def _merge_candidates(ids_a, dst_a, ids_b, dst_b, cand, self_ids,
     return out_i, out_d
 
 
+def _pool_join_hip(xf, ids_a, dst_a, ids_b, dst_b, cand, self_ids, out=None):
+    """_merge_candidates by the pool-join HIP kernels
+    (sptag_amd.pool_join_device): (ids_a, dst_a) is the old pool, whose
+    distances stand, ids_b the new candidates. dst_b=None has their distances
+    to the rows' own vectors computed by the kernel, the search path's f32 L2
+    in place of _exact_l2's gather; a new id that the pool holds already is
+    never computed. One call for any number of rows: the kernel keeps a row's
+    lists in LDS, and the only allocation is the output, or none with
+    `out=(ids, dst)`, which may alias the pool when it is `cand` wide."""
+    if xf.device.type != "cuda":
+        raise RuntimeError('join="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
+    from . import pool_join_device, VT_FLOAT, DM_L2
+    n, d = xf.shape
+    rows = ids_a.shape[0]
+    dev = xf.device
+    xf = xf.contiguous()
+    ids_a = ids_a.to(torch.int32).contiguous()
+    dst_a = dst_a.to(torch.float32).contiguous()
+    ids_b = ids_b.to(torch.int32).contiguous()
+    if dst_b is not None:
+        dst_b = dst_b.to(torch.float32).contiguous()
+    nodes = self_ids.to(torch.int32).contiguous()
+    if (out is not None and out[0].shape == (rows, cand) and
+            out[0].dtype == torch.int32 and out[1].dtype == torch.float32 and
+            out[0].is_contiguous() and out[1].is_contiguous()):
+        out_i, out_d = out
+    else:
+        out_i = torch.empty((rows, cand), dtype=torch.int32, device=dev)
+        out_d = torch.empty((rows, cand), dtype=torch.float32, device=dev)
+    if rows == 0:
+        return out_i, out_d
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    torch.cuda.synchronize(dev)     # the library runs on the default stream
+    pool_join_device(xf.data_ptr(), VT_FLOAT, DM_L2, n, d, nodes.data_ptr(),
+                     rows, ptr(ids_a), ptr(dst_a), ids_a.shape[1], ptr(ids_b),
+                     ptr(dst_b), ids_b.shape[1], cand, out_i.data_ptr(),
+                     out_d.data_ptr(), device=dev.index or 0)
+    return out_i, out_d
+
+
+def _pool_join_torch(xf, ids_a, dst_a, ids_b, dst_b, cand, self_ids, out=None):
+    """the torch join: _exact_l2 where no distances come along, then
+    _merge_candidates"""
+    if dst_b is None:
+        dst_b = _exact_l2(xf, self_ids.long(), ids_b.long())
+    return _merge_candidates(ids_a, dst_a, ids_b, dst_b, cand, self_ids,
+                             out=out)
+
+
+def _join_fn(join):
+    """the pool-growing step by name: f(xf, ids_a, dst_a, ids_b, dst_b, cand,
+    self_ids, out=None), dst_b None for distances still to be computed"""
+    if join == "torch":
+        return _pool_join_torch
+    if join == "hip":
+        return _pool_join_hip
+    raise ValueError(f'join must be "torch" or "hip", got {join!r}')
+
+
 def _bridge_ids(xf, perm, counts):
     """Highway bridges: the reference's search-based RefineNode pool
     (CEF=1000, NeighborhoodGraph.h:535) reaches far beyond a point's own
@@ -644,20 +704,27 @@ def _prune_fn(prune):
 
 def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
                     rng_factor=1.0, seed=2016, device=None, point_chunk=None,
-                    verbose=False, leaf_knn="torch", prune="torch"):
+                    verbose=False, leaf_knn="torch", prune="torch",
+                    join="torch"):
     """Returns (graph, cand_ids, cand_dst), tensors on the device: graph
     int32 [n, degree] (RNG-pruned, ascending, -1 padded) and the [n, cand]
     candidate pools it was pruned from, which the refine steps grow.
     leaf_knn: "torch" (padded GEMM + topk) or "hip" (the grouped-kNN
     kernels; GPU only) for the exact KNN inside the TP-tree leaves.
     prune: "torch" (_rng_prune) or "hip" (the RNG-prune kernels; GPU only)
-    for the RebuildNeighbors step."""
+    for the RebuildNeighbors step.
+    join: "torch" (_exact_l2 + _merge_candidates) or "hip" (the pool-join
+    kernels; GPU only) for every step that grows a candidate pool."""
     if leaf_knn not in _LEAF_KNN:
         raise ValueError(f'leaf_knn must be "torch" or "hip", got {leaf_knn!r}')
     prune_fn = _prune_fn(prune)
+    join_fn = _join_fn(join)
     device, xf, gen = _prologue(vectors, device, seed + 77)
     if prune == "hip" and xf.device.type != "cuda":
         raise RuntimeError('prune="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
+    if join == "hip" and xf.device.type != "cuda":
+        raise RuntimeError('join="hip" needs the vectors on a GPU, got '
                            f"device {xf.device}")
     n = xf.shape[0]
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
@@ -668,11 +735,11 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
         perm, starts, counts = _tpt_leaves(xf, tpt_leaf, gen)
         tids, tdst = _LEAF_KNN[leaf_knn](xf, perm, starts, counts, kper)
         if ids is None:
-            ids, dst = _merge_candidates(tids, tdst, tids[:, :0], tdst[:, :0],
-                                         cand, self_ids)
+            ids, dst = join_fn(xf, tids, tdst, tids[:, :0], tdst[:, :0],
+                               cand, self_ids)
         else:
-            ids, dst = _merge_candidates(ids, dst, tids, tdst, cand, self_ids,
-                                         out=(ids, dst))
+            ids, dst = join_fn(xf, ids, dst, tids, tdst, cand, self_ids,
+                               out=(ids, dst))
         del tids, tdst
         if verbose:
             print(f"  tpt tree {t + 1}/{ntrees} merged ({counts.numel()} leaves)")
@@ -681,7 +748,12 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
     if point_chunk is None:
         # the width _rng_prune will see, so that it never splits a chunk
         wide = cand + (0 if bridge_ids is None else bridge_ids.shape[1])
-        if prune == "hip":
+        if prune == "hip" and join == "hip":
+            # neither a [B, C, C] tensor nor a gather or sort transient: a
+            # chunk allocates its widened pool (ids and distances) and its
+            # slice of the graph, nothing else
+            point_chunk = max(4096, int(2e9 // (wide * 8 + degree * 4)))
+        elif prune == "hip":
             # no [B, C, C] tensor: the merge's transients and the bridges'
             # [B, 8, d] gathers bound the chunk
             point_chunk = max(4096, int(2e9 // (wide * 24 + 64 * xf.shape[1])))
@@ -692,11 +764,9 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
         cid, cdd = ids[s:e], dst[s:e]
         if bridge_ids is not None:
             bi = bridge_ids[s:e]
-            bd = _exact_l2(xf, torch.arange(s, e, device=device), bi.long())
             # widen the pool (cand + bknn) so bridges are never truncated away
-            cid, cdd = _merge_candidates(cid, cdd, bi, bd,
-                                         cid.shape[1] + bi.shape[1],
-                                         self_ids[s:e])
+            cid, cdd = join_fn(xf, cid, cdd, bi, None,
+                               cid.shape[1] + bi.shape[1], self_ids[s:e])
         graph[s:e] = prune_fn(xf, cid, cdd, degree, rng_factor,
                               nodes=self_ids[s:e])
         if verbose and (s // point_chunk) % 20 == 0:
@@ -706,7 +776,8 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
 
 def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
                  rounds=2, hop_sample=8, rng_factor=1.0, device=None,
-                 point_chunk=None, seed=2016, verbose=False, prune="torch"):
+                 point_chunk=None, seed=2016, verbose=False, prune="torch",
+                 join="torch"):
     """Neighborhood refinement: the reference refines each node's edges from
     a CEF-sized candidate pool gathered by searching the index itself
     (NeighborhoodGraph.h:460-560 RefineGraph/RefineNode). Here the pool is
@@ -715,17 +786,29 @@ def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
     Returns (graph int32 [n, degree], cand_ids, cand_dst), all tensors on
     the device (the graph used to come back as a numpy array); a graph
     tensor already on the device, and the pools, are updated in place.
-    prune: as in build_rng_graph; the chunking is the same for both."""
+    prune, join: as in build_rng_graph. The chunk boundaries show in the
+    result (below), so only both on "hip" together change the chunking."""
     prune_fn = _prune_fn(prune)
+    join_fn = _join_fn(join)
     device, xf, _ = _prologue(vectors, device, seed + 123)
     if prune == "hip" and xf.device.type != "cuda":
         raise RuntimeError('prune="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
+    if join == "hip" and xf.device.type != "cuda":
+        raise RuntimeError('join="hip" needs the vectors on a GPU, got '
                            f"device {xf.device}")
     n = xf.shape[0]
     g = torch.as_tensor(graph, device=device)
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
     if point_chunk is None:
-        point_chunk = _prune_chunk(cand, xf.shape[1])
+        if prune == "hip" and join == "hip":
+            # the pools are joined in place and nothing is [B, C, C] or
+            # [B, C, d]: what a chunk allocates is the hop-2 / reverse id
+            # list, about six int32 copies of it while it is put together
+            newc = hop_sample * g.shape[1] + 16
+            point_chunk = max(4096, int(2e9 // (newc * 24 + degree * 4)))
+        else:
+            point_chunk = _prune_chunk(cand, xf.shape[1])
 
     for r in range(rounds):
         # reverse edges (sampled): every edge (i -> j) proposes i to j.
@@ -751,9 +834,9 @@ def refine_graph(vectors, graph, cand_ids, cand_dst, *, degree=32, cand=256,
             hop2 = torch.where((nbr[:, :hop_sample] < 0).repeat_interleave(
                 g.shape[1], dim=1), torch.full_like(hop2, -1), hop2)
             newc = torch.cat([hop2, rev[s:e]], dim=1)
-            newd = _exact_l2(xf, torch.arange(s, e, device=device), newc)
-            cand_ids[s:e], cand_dst[s:e] = _merge_candidates(
-                cand_ids[s:e], cand_dst[s:e], newc, newd, cand, self_ids[s:e])
+            cand_ids[s:e], cand_dst[s:e] = join_fn(
+                xf, cand_ids[s:e], cand_dst[s:e], newc, None, cand,
+                self_ids[s:e], out=(cand_ids[s:e], cand_dst[s:e]))
             g[s:e] = prune_fn(xf, cand_ids[s:e], cand_dst[s:e], degree,
                               rng_factor, nodes=self_ids[s:e])
         if verbose:
@@ -775,7 +858,7 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
                       cand_dst, distmethod, *, algo="BKT", degree=32,
                       cand=256, rounds=1, k=512, max_check=8192,
                       rng_factor=1.0, chunk=0, fill_pruned=False,
-                      verbose=False, prune="torch"):
+                      verbose=False, prune="torch", join="torch"):
     """The reference's own refinement recipe (NeighborhoodGraph.h:460-560
     RefineGraph: every node re-searches the CURRENT index and its edges are
     RNG-rebuilt from the results) — run on the PRODUCT GPU searcher via the
@@ -787,9 +870,11 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
     searcher has no CPU path); vectors_t is the normalized torch tensor on
     the device; graph is a tensor on that device; cand lists are the
     builder's pools (merged in). All three are updated in place and
-    returned. prune: as in build_rng_graph."""
+    returned. prune, join: as in build_rng_graph; the searcher's scratch
+    bounds the chunk with either join."""
     import sptag_amd
     prune_fn = _prune_fn(prune)
+    join_fn = _join_fn(join)
     device = vectors_t.device
     n = vectors_t.shape[0]
     xf = vectors_t if vectors_t.dtype == torch.float32 else vectors_t.float()
@@ -847,8 +932,8 @@ def refine_via_search(vectors_t, tree_start, tree_nodes, graph, cand_ids,
             # pool width FIRST discards exactly those mid-range candidates
             # (measured at 30M: recall 0.86 -> 0.42).
             wide = cand + sv_s.shape[1]
-            wi, wd = _merge_candidates(cand_ids[s0:e0], cand_dst[s0:e0],
-                                       sv_s, sd_s, wide, self_ids[s0:e0])
+            wi, wd = join_fn(xf, cand_ids[s0:e0], cand_dst[s0:e0], sv_s, sd_s,
+                             wide, self_ids[s0:e0])
             graph[s0:e0] = prune_fn(xf, wi, wd, degree, rng_factor,
                                     fill_pruned=fill_pruned,
                                     nodes=self_ids[s0:e0])
@@ -869,12 +954,15 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
                        refine_rounds=0, search_refine_rounds=0, kdt_trees=1,
                        srefine_k=512, srefine_mc=8192, fill_pruned=False,
                        seed=2016, device=None, normalized=False,
-                       verbose=False, leaf_knn="torch", prune="torch"):
+                       verbose=False, leaf_knn="torch", prune="torch",
+                       join="torch"):
     """Full build: returns dict(vectors, tree_start, tree_nodes, graph) ready
     for AnnIndex.FromArrays (vectors already cosine-normalized when needed,
     as the reference stores them on disk). prune: "torch" or "hip" (GPU
-    only), the RebuildNeighbors step of every graph stage."""
+    only), the RebuildNeighbors step of every graph stage; join: likewise,
+    the step that grows the candidate pools."""
     _prune_fn(prune)
+    _join_fn(join)
     if not normalized:
         vectors = normalize_base(vectors, distmethod)
     if algo == "KDT":
@@ -889,19 +977,20 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
     graph, cids, cdst = build_rng_graph(
         vectors, degree=degree, ntrees=ntrees, tpt_leaf=tpt_leaf, cand=cand,
         seed=seed, device=device, verbose=verbose, leaf_knn=leaf_knn,
-        prune=prune)
+        prune=prune, join=join)
     if refine_rounds > 0:
         graph, cids, cdst = refine_graph(
             vectors, graph, cids, cdst, degree=degree, cand=cand,
             rounds=refine_rounds, device=device, seed=seed, verbose=verbose,
-            prune=prune)
+            prune=prune, join=join)
     if search_refine_rounds > 0 and torch.cuda.is_available():
         xt = torch.as_tensor(vectors, device=device or _dev())
         graph, cids, cdst = refine_via_search(
             xt, tree_start, tree_nodes, graph, cids, cdst, distmethod,
             algo=algo, degree=degree, cand=cand, k=srefine_k,
             max_check=srefine_mc, fill_pruned=fill_pruned,
-            rounds=search_refine_rounds, verbose=verbose, prune=prune)
+            rounds=search_refine_rounds, verbose=verbose, prune=prune,
+            join=join)
         del xt
     return {"vectors": vectors, "tree_start": tree_start,
             "tree_nodes": tree_nodes, "graph": graph.cpu().numpy(),

@@ -230,6 +230,25 @@ int launch_rng_prune(int valuetype, int distmethod, const void* vectors, int32_t
                      const float* cand_dists, int32_t ncand, int32_t degree,
                      float rng_factor, int32_t fill_pruned, int32_t* out);
 
+/* Pool join (exact.hip): row r merges its old pool pool_ids[r][0..npool) /
+ * pool_dists (used as given) with new_ids[r][0..nnew), whose distances are
+ * new_dists or, when that is null, the distance of the value type and metric
+ * to vector nodes[r]. An entry with id < 0, id == nodes[r] or a non-finite
+ * given distance is invalid; a new id that is a valid pool entry is dropped;
+ * of several entries of one id inside a list the smallest (dist, position)
+ * stays. out_ids/out_dists[r][0..kout) receive the kout smallest in ascending
+ * (dist, id), then id -1 at +inf, and may be the pool's buffers when kout ==
+ * npool. 0 <= npool, nnew <= POOL_JOIN_MAX_LIST, npool + nnew >= 1, 1 <= kout
+ * <= POOL_JOIN_MAX_LIST; the pool pointers may be null at npool == 0. All
+ * pointers are device memory; with new_dists null every node and every id
+ * >= 0 is inside the vectors. */
+enum { POOL_JOIN_MAX_LIST = 1024 };
+int launch_pool_join(int valuetype, int distmethod, const void* vectors, int32_t dim,
+                     const int32_t* nodes, int32_t nrows, const int32_t* pool_ids,
+                     const float* pool_dists, int32_t npool, const int32_t* new_ids,
+                     const float* new_dists, int32_t nnew, int32_t kout, int32_t* out_ids,
+                     float* out_dists);
+
 /* heap probe (tests/test_gpu_heap_ops.py): a script of nops heap operations
  * (ops[i] != 0: insert {nodes[i], dists[i]}; 0: pop) on a heap of capacity
  * `cap` whose entries [0..lsplit] sit in LDS (lsplit 0: none), run once with

@@ -1591,6 +1591,379 @@ void rng_prune_i8_kernel(const int8_t* __restrict__ vectors, int d,
 }
 
 /* ------------------------------------------------------------------ *
+ * Pool join: merge candidate lists into sorted pools
+ * ------------------------------------------------------------------ *
+ * Row r has a node id, an old pool (ids with distances that stand as given)
+ * and a list of new candidates whose distances are given too or are computed
+ * here, against the node's vector, in the search paths' arithmetic. The row's
+ * output is the kout smallest distinct valid ids in ascending (dist, id),
+ * then id -1 at +inf. A workgroup owns one row.
+ *
+ *   lists    Both id lists become 64-bit keys (id << 32 | entry) in LDS, the
+ *            pool's entries before the new ones, an invalid entry (id < 0,
+ *            the node itself, a non-finite given distance) all ones; the
+ *            given distances go to LDS beside them. Nothing of the row is
+ *            read from global memory after this step but vectors, so the
+ *            output may be the pool's own buffers.
+ *   dedupe   A bitonic sort of the keys puts the entries of one id next to
+ *            each other, the pool's first, in list order. The thread that
+ *            holds the first entry of a run walks it: a run that starts in
+ *            the pool keeps the pool's smallest (dist, position) and drops
+ *            every new entry of that id; a run of new entries keeps its
+ *            smallest given (dist, position), or its first entry when the
+ *            distance is still to be computed. Survivors are appended to the
+ *            final keys: the pool's from slot 0, the new ones from slot
+ *            npool, so the new ones are a dense work list. All of this is
+ *            decided before any vector is touched.
+ *   compute  Tiles of 16 surviving new candidates, one per 16-lane group.
+ *            f32: the tile passes through LDS in slabs of PJ_KS columns
+ *            (float4 loads, the next slab's in flight in registers during
+ *            the math); lane g owns accumulator g of the reference's 16, the
+ *            slabs keep it, and pj_fold_f32 is f32_fold for one pair. The
+ *            node's vector sits in LDS; with a single slab (d <= PJ_KS)
+ *            lane g keeps its columns in registers for the whole row.
+ *            int8: no LDS at all; a lane holds up to five dwords of its
+ *            candidate and of the node's vector (16-byte loads when rows
+ *            are 16-byte multiples), the next tile's in flight, v_dot4c for
+ *            ab and bb in one pass, a DPP fold over the group.
+ *   select   A final key is (order-preserving f32 bits << 32 | id), -0
+ *            folded to +0. A second bitonic sort, over the slots in use
+ *            only, and the first kout keys are the answer.
+ *
+ * Given distances need no compute step: pool_join_given_kernel is lists,
+ * dedupe and select alone, launched with one wave for short lists. */
+
+enum { PJ_MAX_L = POOL_JOIN_MAX_LIST, PJ_T = 16, PJ_KS = 128, PJ_QS = PJ_KS + 16, PJ_I8_NW = 5,
+       PJ_ONE_WAVE_MAX = 512 };
+static_assert((PJ_QS / 16) % 2 == 1, "groups one row apart sit 16 banks apart");
+static_assert(PJ_I8_NW * 16 >= I_MAX_W, "a group's lanes hold a whole int8 row");
+
+static constexpr uint64_t PJ_NONE = ~0ull;
+
+struct PjCtl { int npool; int nnew; };   /* survivors of each list */
+
+struct PjLds { uint32_t ctl, a, b, dd, q, tile, total; };
+
+static constexpr __host__ __device__ int pj_pow2(int n)
+{
+    int p = 2;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+/* given: the new list brings its distances; qwords / twords: dwords of the
+ * node's vector and of a tile slab */
+static constexpr __host__ __device__ PjLds pj_lds(int npool, int nnew, bool given,
+                                                  uint32_t qwords, uint32_t twords)
+{
+    PjLds l = {};
+    const uint32_t P = (uint32_t)pj_pow2(npool + nnew);
+    uint32_t b = 0;
+    l.ctl = b;  b += 16;
+    l.a = b;    b += P * 8;
+    l.b = b;    b += P * 8;
+    l.dd = b;   b += (((uint32_t)npool + (given ? (uint32_t)nnew : 0u)) * 4 + 15) & ~15u;
+    l.q = b;    b += (qwords * 4 + 15) & ~15u;
+    l.tile = b; b += twords * 4;
+    l.total = b;
+    return l;
+}
+static_assert(pj_lds(PJ_MAX_L, PJ_MAX_L, false, MAX_DIM, PJ_T * PJ_QS).total <= RP_LDS_MAX &&
+              pj_lds(PJ_MAX_L, PJ_MAX_L, true, 0, 0).total <= RP_LDS_MAX,
+              "the largest lists at the largest dim fit the prune's LDS budget");
+
+DEV uint64_t pj_pack(float dist, int32_t id)
+{
+    uint32_t b = dist == 0.0f ? 0u : (uint32_t)__float_as_int(dist);
+    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((uint64_t)b << 32) | (uint32_t)id;
+}
+
+DEV float pj_unpack_dist(uint64_t key)
+{
+    const uint32_t b = (uint32_t)(key >> 32);
+    return __int_as_float((int)((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b));
+}
+
+/* ascending bitonic sort of P (a power of two) keys in LDS by the whole
+ * block; starts and ends with a barrier */
+DEV void pj_sort(uint64_t* keys, int P)
+{
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = threadIdx.x; i < (P >> 1); i += blockDim.x) {
+                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+                const uint64_t x = keys[lo], y = keys[hi];
+                if ((x > y) == ((lo & size) == 0)) { keys[lo] = y; keys[hi] = x; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+/* lists and dedupe. Leaves the final keys of the surviving pool entries in
+ * kb[0 .. ctl->npool) and the surviving new entries in kb[npool .. npool +
+ * ctl->nnew), as final keys (GIVEN) or as (all ones << 32 | id); every other
+ * slot of kb[0 .. P) is PJ_NONE. Ends with a barrier. */
+template <bool GIVEN>
+DEV void pj_dedupe(PjCtl* ctl, uint64_t* ka, uint64_t* kb, float* dd, int P, int32_t node,
+                   const int32_t* __restrict__ pool_ids, const float* __restrict__ pool_dists,
+                   int npool, const int32_t* __restrict__ new_ids,
+                   const float* __restrict__ new_dists, int nnew)
+{
+    for (int e = threadIdx.x; e < P; e += blockDim.x) {
+        uint64_t key = PJ_NONE;
+        if (e < npool + nnew) {
+            const bool pool = e < npool;
+            const int32_t id = pool ? pool_ids[e] : new_ids[e - npool];
+            bool valid = id >= 0 && id != node;
+            if (pool || GIVEN) {
+                const float v = pool ? pool_dists[e] : new_dists[e - npool];
+                dd[e] = v;
+                valid = valid && __builtin_isfinite(v);
+            }
+            if (valid) key = ((uint64_t)(uint32_t)id << 32) | (uint32_t)e;
+        }
+        ka[e] = key;
+        kb[e] = PJ_NONE;
+    }
+    if (threadIdx.x == 0) { ctl->npool = 0; ctl->nnew = 0; }
+    pj_sort(ka, P);
+    for (int i = threadIdx.x; i < P; i += blockDim.x) {
+        const uint64_t key = ka[i];
+        if (key == PJ_NONE) continue;
+        const uint32_t id = (uint32_t)(key >> 32);
+        if (i > 0 && (uint32_t)(ka[i - 1] >> 32) == id) continue;   /* not a run's first */
+        const int e = (int)(uint32_t)key;
+        const bool pool = e < npool;
+        float best = 0.0f;
+        if (pool || GIVEN) {
+            best = dd[e];
+            for (int j = i + 1; j < P; j++) {
+                const uint64_t kj = ka[j];
+                const int ej = (int)(uint32_t)kj;
+                if ((uint32_t)(kj >> 32) != id || (pool && ej >= npool)) break;
+                const float v = dd[ej];
+                if (v < best) best = v;      /* entries come in list order */
+            }
+        }
+        if (pool)
+            kb[atomicAdd(&ctl->npool, 1)] = pj_pack(best, (int32_t)id);
+        else
+            kb[npool + atomicAdd(&ctl->nnew, 1)] =
+                GIVEN ? pj_pack(best, (int32_t)id) : (0xffffffffull << 32) | id;
+    }
+    __syncthreads();
+}
+
+/* select: sort the slots in use and write the row. Every new survivor has
+ * its final key. */
+DEV void pj_select(const PjCtl* ctl, uint64_t* kb, int npool, int kout,
+                   int32_t* __restrict__ out_ids, float* __restrict__ out_dists)
+{
+    const int nn = ctl->nnew, total = ctl->npool + nn;
+    const int P = pj_pow2(npool + nn);
+    pj_sort(kb, P);
+    for (int i = threadIdx.x; i < kout; i += blockDim.x) {
+        const bool in = i < total;
+        const uint64_t key = in ? kb[i] : PJ_NONE;
+        out_ids[i] = in ? (int32_t)(uint32_t)key : -1;
+        out_dists[i] = in ? pj_unpack_dist(key) : __builtin_inff();
+    }
+}
+
+template <int CTRL>
+DEV int dpp_i(int v)
+{
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
+}
+
+/* f32_fold for one pair: lane g's accumulator `a` of the reference's 16,
+ * q and r at the first column of the last slab, which starts at column k0.
+ * The distance, on lane g == 0 of the group. */
+template <int DM>
+DEV float pj_fold_f32(float a, const float* q, const float* r, int k0, int d, int g)
+{
+    const int nd16 = d & ~15, nd8 = d & ~7, nd4 = d & ~3;
+    const int tc = nd16 - k0;
+    a = a + dpp<DPP_ROW_SHL8>(a);
+    if (nd8 > nd16) a = g < 8 ? xstep<DM>(q[tc + g], r[tc + g], a) : a;
+    a = a + dpp<DPP_ROW_SHL4>(a);
+    if (nd4 > nd8)
+        a = g < 4 ? xstep<DM>(q[tc + (nd8 - nd16) + g], r[tc + (nd8 - nd16) + g], a) : a;
+    float s = ((dpp<DPP_QUAD0>(a) + dpp<DPP_QUAD1>(a)) + dpp<DPP_QUAD2>(a)) + dpp<DPP_QUAD3>(a);
+    for (int c = nd4; c < d; c++) s = xstep<DM>(q[c - k0], r[c - k0], s);
+    return (DM == DM_L2) ? s : 1.0f - s;
+}
+
+__global__ __launch_bounds__(XTHREADS)
+void pool_join_given_kernel(const int32_t* __restrict__ nodes,
+                            const int32_t* pool_ids, const float* pool_dists, int npool,
+                            const int32_t* __restrict__ new_ids,
+                            const float* __restrict__ new_dists, int nnew, int kout,
+                            int32_t* out_ids, float* out_dists)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const PjLds L = pj_lds(npool, nnew, true, 0, 0);
+    PjCtl* ctl = (PjCtl*)(xlds + L.ctl);
+    uint64_t* kb = (uint64_t*)(xlds + L.b);
+    const size_t row = blockIdx.x;
+    pj_dedupe<true>(ctl, (uint64_t*)(xlds + L.a), kb, (float*)(xlds + L.dd),
+                    pj_pow2(npool + nnew), nodes[row], pool_ids + row * npool,
+                    pool_dists + row * npool, npool, new_ids + row * nnew,
+                    new_dists + row * nnew, nnew);
+    pj_select(ctl, kb, npool, kout, out_ids + row * kout, out_dists + row * kout);
+}
+
+/* ONE: d <= PJ_KS, a single slab, the node's columns in registers */
+template <int DM, bool ONE>
+__global__ __launch_bounds__(XTHREADS)
+void pool_join_f32_kernel(const float* __restrict__ vectors, int d,
+                          const int32_t* __restrict__ nodes,
+                          const int32_t* pool_ids, const float* pool_dists, int npool,
+                          const int32_t* __restrict__ new_ids, int nnew, int kout,
+                          int32_t* out_ids, float* out_dists)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const PjLds L = pj_lds(npool, nnew, false, (uint32_t)((d + 3) & ~3), PJ_T * PJ_QS);
+    PjCtl* ctl = (PjCtl*)(xlds + L.ctl);
+    uint64_t* kb = (uint64_t*)(xlds + L.b);
+    float* qv = (float*)(xlds + L.q);
+    float* tbuf = (float*)(xlds + L.tile);
+    const int tid = threadIdx.x, g = tid & 15, lr = tid >> 4;
+    const size_t row = blockIdx.x;
+    const int32_t node = nodes[row];
+    const bool vec = (d & 3) == 0 && ((uintptr_t)vectors & 15) == 0;
+
+    /* the node's vector; the barriers of the dedupe stand behind it */
+    for (int c = 4 * tid; c < d; c += 4 * XTHREADS)
+        *(float4*)(qv + c) = rp_cols4(vectors + (size_t)node * d, d, c, vec);
+    pj_dedupe<false>(ctl, (uint64_t*)(xlds + L.a), kb, (float*)(xlds + L.dd),
+                     pj_pow2(npool + nnew), node, pool_ids + row * npool,
+                     pool_dists + row * npool, npool, new_ids + row * nnew, nullptr, nnew);
+
+    const int nn = ctl->nnew;
+    const int nslab = (d + PJ_KS - 1) / PJ_KS, nstep = ((nn + PJ_T - 1) / PJ_T) * nslab;
+    float xq[PJ_KS / 16];
+    if constexpr (ONE) {
+#pragma unroll
+        for (int c = 0; c < PJ_KS / 16; c++) xq[c] = c * 16 + 16 <= d ? qv[c * 16 + g] : 0.0f;
+    }
+    /* this thread's columns 4*(g + 16*k) of candidate lr of a tile, one slab */
+    float4 pre[PJ_KS / 64];
+    auto slab_load = [&](int step) {
+        const int t = step / nslab, slab = step - t * nslab, w = t * PJ_T + lr;
+        const float* p = w < nn ? vectors + (size_t)(uint32_t)kb[npool + w] * d : nullptr;
+#pragma unroll
+        for (int k = 0; k < PJ_KS / 64; k++)
+            pre[k] = rp_cols4(p, d, slab * PJ_KS + 4 * (g + 16 * k), vec);
+    };
+    if (nstep > 0) slab_load(0);
+    float acc = 0.0f;
+    for (int step = 0; step < nstep; step++) {
+        const int t = step / nslab, slab = step - t * nslab;
+#pragma unroll
+        for (int k = 0; k < PJ_KS / 64; k++)
+            *(float4*)(tbuf + lr * PJ_QS + 4 * (g + 16 * k)) = pre[k];
+        __syncthreads();
+        if (step + 1 < nstep) slab_load(step + 1);   /* in flight during the math */
+        const float* qb = qv + slab * PJ_KS;
+        const float* rb = tbuf + lr * PJ_QS;
+        if (slab == 0) acc = 0.0f;
+#pragma unroll
+        for (int c = 0; c < PJ_KS / 16; c++) {
+            if (slab * PJ_KS + c * 16 + 16 > d) break;
+            acc = xstep<DM>(ONE ? xq[c] : qb[c * 16 + g], rb[c * 16 + g], acc);
+        }
+        if (slab == nslab - 1) {
+            const float dist = pj_fold_f32<DM>(acc, qb, rb, slab * PJ_KS, d, g);
+            const int w = t * PJ_T + lr;
+            if (g == 0 && w < nn) kb[npool + w] = pj_pack(dist, (int32_t)(uint32_t)kb[npool + w]);
+        }
+        __syncthreads();    /* the slab is free */
+    }
+    pj_select(ctl, kb, npool, kout, out_ids + row * kout, out_dists + row * kout);
+}
+
+template <int DM>
+__global__ __launch_bounds__(XTHREADS)
+void pool_join_i8_kernel(const int8_t* __restrict__ vectors, int d,
+                         const int32_t* __restrict__ nodes,
+                         const int32_t* pool_ids, const float* pool_dists, int npool,
+                         const int32_t* __restrict__ new_ids, int nnew, int kout,
+                         int32_t* out_ids, float* out_dists)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const PjLds L = pj_lds(npool, nnew, false, 0, 0);
+    PjCtl* ctl = (PjCtl*)(xlds + L.ctl);
+    uint64_t* kb = (uint64_t*)(xlds + L.b);
+    const int tid = threadIdx.x, g = tid & 15, lr = tid >> 4;
+    const size_t row = blockIdx.x;
+    const int32_t node = nodes[row];
+    const int W = (d + 3) >> 2;
+    /* a lane's dwords of a row: 4g .. 4g+3 by one 16-byte load when rows are
+     * 16-byte multiples, else g + 16*j, loaded whole or packed from bytes.
+     * Both operands of a dot use the same assignment, which is all it needs. */
+    const bool v16 = (d & 15) == 0 && ((uintptr_t)vectors & 15) == 0;
+    const bool v4 = (d & 3) == 0 && ((uintptr_t)vectors & 3) == 0;
+    auto row_load = [&](int32_t id, uint32_t (&v)[PJ_I8_NW]) {
+#pragma unroll
+        for (int j = 0; j < PJ_I8_NW; j++) v[j] = 0u;
+        if (id < 0) return;
+        if (v16) {
+            if (4 * g < W) {
+                const uint4 x = *(const uint4*)(vectors + (size_t)id * d + 16 * g);
+                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+            }
+            return;
+        }
+#pragma unroll
+        for (int j = 0; j < PJ_I8_NW; j++) {
+            const int w = g + 16 * j;
+            if (w < W)
+                v[j] = v4 ? ((const uint32_t*)(vectors + (size_t)id * d))[w]
+                          : i8_pack_dword(vectors, id, w, d);
+        }
+    };
+    uint32_t qd[PJ_I8_NW], cur[PJ_I8_NW], nxt[PJ_I8_NW];
+    row_load(node, qd);
+    int aa = 0;
+#pragma unroll
+    for (int j = 0; j < PJ_I8_NW; j++)
+        aa = __builtin_amdgcn_sdot4((int)qd[j], (int)qd[j], aa, false);
+    pj_dedupe<false>(ctl, (uint64_t*)(xlds + L.a), kb, (float*)(xlds + L.dd),
+                     pj_pow2(npool + nnew), node, pool_ids + row * npool,
+                     pool_dists + row * npool, npool, new_ids + row * nnew, nullptr, nnew);
+
+    const int nn = ctl->nnew, ntile = (nn + PJ_T - 1) / PJ_T;
+    auto cand_load = [&](int t, uint32_t (&v)[PJ_I8_NW]) {
+        const int w = t * PJ_T + lr;
+        row_load(w < nn ? (int32_t)(uint32_t)kb[npool + w] : -1, v);
+    };
+    if (ntile > 0) cand_load(0, nxt);
+    for (int t = 0; t < ntile; t++) {
+#pragma unroll
+        for (int j = 0; j < PJ_I8_NW; j++) cur[j] = nxt[j];
+        if (t + 1 < ntile) cand_load(t + 1, nxt);    /* in flight during the dots */
+        int ab = 0, bb = 0;
+#pragma unroll
+        for (int j = 0; j < PJ_I8_NW; j++) {
+            ab = __builtin_amdgcn_sdot4((int)qd[j], (int)cur[j], ab, false);
+            if (DM == DM_L2) bb = __builtin_amdgcn_sdot4((int)cur[j], (int)cur[j], bb, false);
+        }
+        int s = (DM == DM_L2) ? aa - 2 * ab + bb : ab;    /* this lane's share */
+        s += dpp_i<DPP_ROW_SHL8>(s);
+        s += dpp_i<DPP_ROW_SHL4>(s);
+        s = dpp_i<DPP_QUAD0>(s) + dpp_i<DPP_QUAD1>(s) + dpp_i<DPP_QUAD2>(s) + dpp_i<DPP_QUAD3>(s);
+        const float dist = (DM == DM_L2) ? (float)s : (float)(16129 - s);
+        const int w = t * PJ_T + lr;
+        if (g == 0 && w < nn) kb[npool + w] = pj_pack(dist, (int32_t)(uint32_t)kb[npool + w]);
+    }
+    pj_select(ctl, kb, npool, kout, out_ids + row * kout, out_dists + row * kout);
+}
+
+/* ------------------------------------------------------------------ *
  * launchers
  * ------------------------------------------------------------------ */
 
@@ -1691,6 +2064,48 @@ int launch_rng_prune(int vt, int dm, const void* vectors, int32_t dim, const int
         hipLaunchKernelGGL(kernel, grid, dim3(64), rp_lds(MAX_DEG * wl, RI_T * wl, ncand).total,
                            nullptr, (const int8_t*)vectors, dim, nodes, cand_ids, cand_dists,
                            ncand, degree, rng_factor, fill_pruned, out);
+    }
+    return (int)hipGetLastError();
+}
+
+int launch_pool_join(int vt, int dm, const void* vectors, int32_t dim, const int32_t* nodes,
+                     int32_t nrows, const int32_t* pool_ids, const float* pool_dists,
+                     int32_t npool, const int32_t* new_ids, const float* new_dists,
+                     int32_t nnew, int32_t kout, int32_t* out_ids, float* out_dists)
+{
+    /* the kernels index nothing outside these bounds */
+    if (nrows < 1 || npool < 0 || npool > PJ_MAX_L || nnew < 0 || nnew > PJ_MAX_L ||
+        npool + nnew < 1 || kout < 1 || kout > PJ_MAX_L)
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(nrows);
+    if (new_dists) {
+        /* lists and sorts only: one wave does a short row */
+        const dim3 block(npool + nnew <= PJ_ONE_WAVE_MAX ? 64 : XTHREADS);
+        hipLaunchKernelGGL(pool_join_given_kernel, grid, block,
+                           pj_lds(npool, nnew, true, 0, 0).total, nullptr, nodes, pool_ids,
+                           pool_dists, npool, new_ids, new_dists, nnew, kout, out_ids,
+                           out_dists);
+        return (int)hipGetLastError();
+    }
+    if (dim < 1 || dim > MAX_DIM || (vt != VT_FLOAT && vt != VT_INT8) ||
+        (vt == VT_INT8 && dim > 4 * I_MAX_W))
+        return (int)hipErrorInvalidValue;
+    if (vt == VT_FLOAT) {
+        const bool one = dim <= PJ_KS;
+        auto kernel = dm == DM_L2 ? (one ? pool_join_f32_kernel<DM_L2, true>
+                                         : pool_join_f32_kernel<DM_L2, false>)
+                                  : (one ? pool_join_f32_kernel<DM_COSINE, true>
+                                         : pool_join_f32_kernel<DM_COSINE, false>);
+        hipLaunchKernelGGL(kernel, grid, dim3(XTHREADS),
+                           pj_lds(npool, nnew, false, (uint32_t)((dim + 3) & ~3),
+                                  PJ_T * PJ_QS).total,
+                           nullptr, (const float*)vectors, dim, nodes, pool_ids, pool_dists,
+                           npool, new_ids, nnew, kout, out_ids, out_dists);
+    } else {
+        auto kernel = dm == DM_L2 ? pool_join_i8_kernel<DM_L2> : pool_join_i8_kernel<DM_COSINE>;
+        hipLaunchKernelGGL(kernel, grid, dim3(XTHREADS), pj_lds(npool, nnew, false, 0, 0).total,
+                           nullptr, (const int8_t*)vectors, dim, nodes, pool_ids, pool_dists,
+                           npool, new_ids, nnew, kout, out_ids, out_dists);
     }
     return (int)hipGetLastError();
 }

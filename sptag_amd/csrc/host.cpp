@@ -1141,6 +1141,109 @@ int sptag_amd_rng_prune(SptagAmdIndex* ix, const int32_t* nodes, int32_t nrows,
     return SPTAG_AMD_OK;
 }
 
+/* what both pool-join entries can check from the host */
+static bool pool_join_args_ok(const void* nodes, int32_t nrows, const void* pool_ids,
+                              const void* pool_dists, int32_t npool, const void* new_ids,
+                              int32_t nnew, int32_t kout, const void* out_ids,
+                              const void* out_dists)
+{
+    return nodes && out_ids && out_dists && nrows >= 1 && npool >= 0 &&
+           npool <= POOL_JOIN_MAX_LIST && nnew >= 0 && nnew <= POOL_JOIN_MAX_LIST &&
+           npool + nnew >= 1 && kout >= 1 && kout <= POOL_JOIN_MAX_LIST &&
+           (npool == 0 || (pool_ids && pool_dists)) && (nnew == 0 || new_ids);
+}
+
+/* pool join into device buffers, arguments checked; `device` is current.
+ * Returns once the output is complete. */
+static int pool_join_core(const void* d_vectors, int vt, int dm, int32_t dim,
+                          const int32_t* d_nodes, int32_t nrows, const int32_t* d_pool_ids,
+                          const float* d_pool_dists, int32_t npool, const int32_t* d_new_ids,
+                          const float* d_new_dists, int32_t nnew, int32_t kout,
+                          int32_t* d_out_ids, float* d_out_dists)
+{
+    /* an empty new list has nothing to compute: the lists-only kernel, with
+     * any non-null pointer standing for its absent distances */
+    if (nnew == 0) {
+        d_new_ids = d_nodes;
+        d_new_dists = (const float*)d_nodes;
+    }
+    int err = launch_pool_join(vt, dm, d_vectors, dim, d_nodes, nrows, d_pool_ids,
+                               d_pool_dists, npool, d_new_ids, d_new_dists, nnew, kout,
+                               d_out_ids, d_out_dists);
+    if (err != 0) {
+        fprintf(stderr, "sptag_amd: pool join launch failed %d\n", err);
+        return SPTAG_AMD_ERR_INTERNAL;
+    }
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+int sptag_amd_pool_join_device(int device, const void* d_vectors, int valuetype,
+                               int distmethod, int32_t n, int32_t dim,
+                               const int32_t* d_nodes, int32_t nrows,
+                               const int32_t* d_pool_ids, const float* d_pool_dists,
+                               int32_t npool, const int32_t* d_new_ids,
+                               const float* d_new_dists, int32_t nnew, int32_t kout,
+                               int32_t* d_out_ids, float* d_out_dists)
+{
+    if (!d_vectors || n < 1 || dim < 1 || dim > MAX_DIM ||
+        (valuetype != VT_FLOAT && valuetype != VT_INT8) ||
+        (distmethod != DM_L2 && distmethod != DM_COSINE) ||
+        (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) ||
+        !pool_join_args_ok(d_nodes, nrows, d_pool_ids, d_pool_dists, npool, d_new_ids, nnew,
+                           kout, d_out_ids, d_out_dists))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    return pool_join_core(d_vectors, valuetype, distmethod, dim, d_nodes, nrows, d_pool_ids,
+                          d_pool_dists, npool, d_new_ids, d_new_dists, nnew, kout, d_out_ids,
+                          d_out_dists);
+}
+
+int sptag_amd_pool_join(SptagAmdIndex* ix, const int32_t* nodes, int32_t nrows,
+                        const int32_t* pool_ids, const float* pool_dists, int32_t npool,
+                        const int32_t* new_ids, const float* new_dists, int32_t nnew,
+                        int32_t kout, int32_t* out_ids, float* out_dists)
+{
+    if (!ix || !pool_join_args_ok(nodes, nrows, pool_ids, pool_dists, npool, new_ids, nnew,
+                                  kout, out_ids, out_dists))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available() || !ix->d_vectors) return SPTAG_AMD_ERR_NOGPU;
+    std::lock_guard<std::mutex> g(ix->lock);
+    const size_t npc = (size_t)nrows * npool, nnc = (size_t)nrows * nnew,
+                 nout = (size_t)nrows * kout;
+    for (int32_t r = 0; r < nrows; r++)
+        if (nodes[r] < 0 || nodes[r] >= ix->n) return SPTAG_AMD_ERR_PARAM;
+    for (size_t i = 0; i < npc; i++)
+        if (pool_ids[i] >= ix->n) return SPTAG_AMD_ERR_PARAM;
+    for (size_t i = 0; i < nnc; i++)
+        if (new_ids[i] >= ix->n) return SPTAG_AMD_ERR_PARAM;
+    HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
+
+    DevBuf d_nodes, d_pi, d_pd, d_ni, d_nd, d_oi, d_od;
+    int rc;
+    if ((rc = dev_upload(d_nodes, nodes, (size_t)nrows * 4)) != SPTAG_AMD_OK) return rc;
+    if (npc && (rc = dev_upload(d_pi, pool_ids, npc * 4)) != SPTAG_AMD_OK) return rc;
+    if (npc && (rc = dev_upload(d_pd, pool_dists, npc * 4)) != SPTAG_AMD_OK) return rc;
+    if (nnc && (rc = dev_upload(d_ni, new_ids, nnc * 4)) != SPTAG_AMD_OK) return rc;
+    if (nnc && new_dists && (rc = dev_upload(d_nd, new_dists, nnc * 4)) != SPTAG_AMD_OK)
+        return rc;
+    HIP_OR_FAIL(d_oi.alloc(nout * 4), SPTAG_AMD_ERR_OOM);
+    HIP_OR_FAIL(d_od.alloc(nout * 4), SPTAG_AMD_ERR_OOM);
+    rc = pool_join_core(ix->d_vectors.as(), ix->vt, ix->dm, ix->dim, d_nodes.as<int32_t>(),
+                        nrows, npc ? d_pi.as<int32_t>() : nullptr,
+                        npc ? d_pd.as<float>() : nullptr, npool,
+                        nnc ? d_ni.as<int32_t>() : nullptr,
+                        nnc && new_dists ? d_nd.as<float>() : nullptr, nnew, kout,
+                        d_oi.as<int32_t>(), d_od.as<float>());
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(hipMemcpy(out_ids, d_oi.as(), nout * 4, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipMemcpy(out_dists, d_od.as(), nout * 4, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
 /* Host-side distance restatements for the add path's edge arithmetic
  * (RebuildNeighbors / InsertNeighbors recompute pair distances on the
  * host, as the reference does on CPU): same rounding contracts as the
