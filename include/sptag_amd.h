@@ -268,6 +268,78 @@ int sptag_amd_pool_join_device(int device, const void* d_vectors, int valuetype,
                                const float* d_new_dists, int32_t nnew, int32_t kout,
                                int32_t* d_out_ids, float* d_out_dists);
 
+/* K-means assign: one KmeansAssign pass (the reference's BKTree.h:220-311)
+ * over many independent segments, the index builder's tree step. Segment s is
+ * members[seg_starts[s] .. + seg_sizes[s]) (vector ids; an id may occur twice,
+ * in one segment or in several; a size of 0 is allowed; segments do not
+ * overlap) with centers centers[s][0..ncenters[s]) of centers[nseg][kmax][dim],
+ * which have the value type of the vectors; rows at or past ncenters[s] are
+ * never read. 1 <= ncenters[s] <= kmax, 1 <= kmax <= 64. prev_counts
+ * [nseg][kmax] and lambdas [nseg] are both given or both null (no penalty).
+ * The member at position i of segment s, with vector x:
+ *   - For k = 0 .. ncenters[s] - 1 in order, dist_k = D(x, center_k) +
+ *     lambdas[s] * (float)prev_counts[s][k]. D is the search paths' distance
+ *     for the value type and metric, bit for bit (f32 in the reference's
+ *     16/8/4-accumulator order, 1 - dot for cosine; int8 exact integers, 16129
+ *     - dot for cosine); the penalty is an f32 product rounded once, then an
+ *     f32 sum rounded once, never fused; with lambdas null nothing is added.
+ *   - Center k replaces the choice iff dist_k > -MaxDist && dist_k < smallest,
+ *     from (label 0, smallest = MaxDist), MaxDist = FLT_MAX / 10: ties go to
+ *     the lowest k, a NaN or a value at or above MaxDist is never chosen, and a
+ *     member no center qualifies for ends at label 0 with distance MaxDist.
+ * out_labels[nmembers] / out_dists[nmembers] (may be null) receive the choice
+ * and its `smallest` at the member's place in the list; places in no segment
+ * are untouched. Per segment and center below ncenters[s] (entries at or past
+ * it are untouched): out_counts[nseg][kmax], the members of the center;
+ * out_cluster_idx / out_cluster_dist, one extreme member as a vector id with
+ * its `smallest`: with update == 1 the member of largest `smallest`, ties to
+ * the smallest position, with update == 0 the member of smallest `smallest`,
+ * ties to the largest position (the reference's > and <= over ascending
+ * positions); an empty center gets -1 with -MaxDist (update 1) or MaxDist.
+ * out_sums[nseg][kmax][dim] (f32) is written with update == 1 only and may be
+ * null otherwise: the sum of the center's members' vectors, int8 as integers
+ * rounded to f32 once, f32 in an order that is the kernel's but fixed, so
+ * equal calls give equal bytes; all zeros for an empty center. Dividing and
+ * casting the sums into the next centers stays with the caller.
+ * The handle form takes host arrays and uses the handle's vectors, value type
+ * and metric; the delete set, the tree and the graph are not consulted (BKT
+ * and KDT handles alike). Computed by the k-means-assign kernels of
+ * exact.hip: a workgroup owns a run of one segment's members, keeps the
+ * centers in LDS, reads each vector once for distance and sum where LDS
+ * allows, and leaves counts and extremes by integer atomics and sums as
+ * partials that a second kernel adds in list order. Returns
+ * SPTAG_AMD_ERR_PARAM, with the outputs untouched, for a null required
+ * pointer, kmax or an ncenters[s] out of range, nseg < 1, a negative start or
+ * size, a segment past nmembers, overlapping segments, one of prev_counts /
+ * lambdas without the other, update not 0 or 1, update == 1 with null sums,
+ * and a member outside [0, n). */
+int sptag_amd_kmeans_assign(SptagAmdIndex* idx, const int32_t* members, int32_t nmembers,
+                            const int32_t* seg_starts, const int32_t* seg_sizes,
+                            const int32_t* ncenters, int32_t nseg, const void* centers,
+                            int32_t kmax, const int32_t* prev_counts, const float* lambdas,
+                            int32_t update, int32_t* out_labels, float* out_dists,
+                            int32_t* out_counts, int32_t* out_cluster_idx,
+                            float* out_cluster_dist, float* out_sums);
+/* The same without a handle: d_vectors ([n][dim] of valuetype), d_members,
+ * d_centers, d_prev_counts, d_lambdas and the outputs are HIP device buffers
+ * on `device`; seg_starts, seg_sizes and ncenters are host arrays. It checks
+ * what the host can see (the pointers, the segments, kmax and ncenters, value
+ * type, metric, 1 <= dim <= 4096, the int8 dim guard of the create calls) and
+ * returns SPTAG_AMD_ERR_PARAM for those. That every member is inside [0, n)
+ * is the CALLER'S to guarantee: an id outside makes the kernels read outside
+ * d_vectors. Runs on the default stream and returns after a device
+ * synchronise. */
+int sptag_amd_kmeans_assign_device(int device, const void* d_vectors, int valuetype,
+                                   int distmethod, int32_t n, int32_t dim,
+                                   const int32_t* d_members, int32_t nmembers,
+                                   const int32_t* seg_starts, const int32_t* seg_sizes,
+                                   const int32_t* ncenters, int32_t nseg,
+                                   const void* d_centers, int32_t kmax,
+                                   const int32_t* d_prev_counts, const float* d_lambdas,
+                                   int32_t update, int32_t* d_out_labels, float* d_out_dists,
+                                   int32_t* d_out_counts, int32_t* d_out_cluster_idx,
+                                   float* d_out_cluster_dist, float* d_out_sums);
+
 /* Iterative (streaming) search — mirrors the reference's ResultIterator /
  * SearchIndexIterativeNext protocol (inc/Core/VectorIndex.h:43-49,
  * src/Core/ResultIterator.cpp) over a BATCH of nq per-query iterators whose

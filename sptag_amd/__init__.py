@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "group_knn_device",
-           "rng_prune_device", "pool_join_device",
+           "rng_prune_device", "pool_join_device", "kmeans_assign_device",
            "MetadataSet", "load_library", "gpu_available", "SptagAmdError"]
 
 _LIB = None
@@ -111,6 +111,18 @@ def load_library():
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
         ctypes.c_void_p]
+    lib.sptag_amd_kmeans_assign.restype = ctypes.c_int
+    lib.sptag_amd_kmeans_assign.argtypes = (
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] +
+        [ctypes.c_void_p] * 3 + [ctypes.c_int32, ctypes.c_void_p,
+                                 ctypes.c_int32, ctypes.c_void_p,
+                                 ctypes.c_void_p, ctypes.c_int32] +
+        [ctypes.c_void_p] * 6)
+    lib.sptag_amd_kmeans_assign_device.restype = ctypes.c_int
+    lib.sptag_amd_kmeans_assign_device.argtypes = (
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+         ctypes.c_int32, ctypes.c_int32] +
+        lib.sptag_amd_kmeans_assign.argtypes[1:])
     lib.sptag_amd_save_index.restype = ctypes.c_int
     lib.sptag_amd_save_index.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     for f in ["num_vectors", "dim", "valuetype", "distmethod", "degree",
@@ -470,6 +482,59 @@ class AnnIndex:
             raise SptagAmdError(rc, "pool_join")
         return ids, dists
 
+    def KmeansAssign(self, members, seg_starts, seg_sizes, centers, ncenters,
+                     update, prev_counts=None, lambdas=None):
+        """One k-means assign pass over segments of a member list: segment s
+        is members[seg_starts[s] : seg_starts[s] + seg_sizes[s]] (vector ids)
+        with centers centers[s, :ncenters[s]] of centers [nseg, kmax, dim] in
+        the vectors' value type. A member goes to the center of smallest
+        handle search distance plus lambdas[s] * prev_counts[s, k] (both or
+        neither given), ties to the lowest k. Returns (labels int32
+        [nmembers], dists f32 [nmembers], counts int32 [nseg, kmax],
+        cluster_idx int32 [nseg, kmax], cluster_dist f32 [nseg, kmax], sums):
+        per center one extreme member as a vector id, the farthest with
+        update, the nearest without, -1 for an empty center; sums f32
+        [nseg, kmax, dim] of the members' vectors with update, else None.
+        Entries of centers at or past ncenters[s], and labels of places in no
+        segment, come back as 0."""
+        members = np.ascontiguousarray(members, dtype=np.int32)
+        seg_starts = np.ascontiguousarray(seg_starts, dtype=np.int32)
+        seg_sizes = np.ascontiguousarray(seg_sizes, dtype=np.int32)
+        ncenters = np.ascontiguousarray(ncenters, dtype=np.int32)
+        centers = np.ascontiguousarray(
+            centers, dtype=np.float32 if self.valuetype == VT_FLOAT else np.int8)
+        if (members.ndim != 1 or seg_starts.ndim != 1 or centers.ndim != 3 or
+                not (seg_starts.shape == seg_sizes.shape == ncenters.shape
+                     == centers.shape[:1]) or centers.shape[2] != self.dim):
+            raise ValueError("members [nmembers], seg_starts, seg_sizes and "
+                             "ncenters [nseg], centers [nseg, kmax, dim] "
+                             "expected")
+        nseg, kmax = centers.shape[:2]
+        if (prev_counts is None) != (lambdas is None):
+            raise ValueError("prev_counts and lambdas go together")
+        if lambdas is not None:
+            prev_counts = np.ascontiguousarray(prev_counts, dtype=np.int32)
+            lambdas = np.ascontiguousarray(lambdas, dtype=np.float32)
+            if prev_counts.shape != (nseg, kmax) or lambdas.shape != (nseg,):
+                raise ValueError("prev_counts [nseg, kmax] and lambdas [nseg] "
+                                 "expected")
+        labels = np.zeros(members.size, dtype=np.int32)
+        dists = np.zeros(members.size, dtype=np.float32)
+        counts = np.zeros((nseg, kmax), dtype=np.int32)
+        cidx = np.zeros((nseg, kmax), dtype=np.int32)
+        cdist = np.zeros((nseg, kmax), dtype=np.float32)
+        sums = (np.zeros((nseg, kmax, self.dim), dtype=np.float32)
+                if update else None)
+        p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        rc = self._lib.sptag_amd_kmeans_assign(
+            self._h, p(members), members.size, p(seg_starts), p(seg_sizes),
+            p(ncenters), nseg, p(centers), kmax, p(prev_counts), p(lambdas),
+            1 if update else 0, p(labels), p(dists), p(counts), p(cidx),
+            p(cdist), p(sums))
+        if rc != 0:
+            raise SptagAmdError(rc, "kmeans_assign")
+        return labels, dists, counts, cidx, cdist, sums
+
     def Add(self, vectors, normalized=False):
         """Online add (reference AddIndex semantics below the tree-rebuild
         threshold); runs GPU refine searches per added vector."""
@@ -584,6 +649,41 @@ def pool_join_device(d_vectors_ptr, valuetype, distmethod, n, dim,
         vp(d_out_ids_ptr), vp(d_out_dists_ptr))
     if rc != 0:
         raise SptagAmdError(rc, "pool_join_device")
+
+
+def kmeans_assign_device(d_vectors_ptr, valuetype, distmethod, n, dim,
+                         d_members_ptr, nmembers, seg_starts, seg_sizes,
+                         ncenters, d_centers_ptr, kmax, d_prev_counts_ptr,
+                         d_lambdas_ptr, update, d_labels_ptr, d_dists_ptr,
+                         d_counts_ptr, d_cluster_idx_ptr, d_cluster_dist_ptr,
+                         d_sums_ptr, device=0):
+    """AnnIndex.KmeansAssign without a handle, on HIP device addresses (e.g.
+    torch tensors' .data_ptr()): vectors [n, dim] and centers [nseg, kmax,
+    dim] of `valuetype`, int32 members [nmembers], outputs int32 / float32
+    [nmembers] and [nseg, kmax], float32 sums [nseg, kmax, dim]. seg_starts,
+    seg_sizes and ncenters are host arrays. d_prev_counts_ptr and
+    d_lambdas_ptr are both None or both given; d_dists_ptr may be None, and
+    d_sums_ptr without update. The caller guarantees that every member is
+    inside [0, n)."""
+    seg_starts = np.ascontiguousarray(seg_starts, dtype=np.int32)
+    seg_sizes = np.ascontiguousarray(seg_sizes, dtype=np.int32)
+    ncenters = np.ascontiguousarray(ncenters, dtype=np.int32)
+    if not (seg_starts.shape == seg_sizes.shape == ncenters.shape) or \
+            seg_starts.ndim != 1:
+        raise ValueError("seg_starts, seg_sizes and ncenters must be 1-d and "
+                         "of one length")
+    dm = {"L2": DM_L2, "Cosine": DM_COSINE}.get(distmethod, distmethod)
+    vp = lambda a: ctypes.c_void_p(a) if a else None
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    rc = load_library().sptag_amd_kmeans_assign_device(
+        device, vp(d_vectors_ptr), valuetype, dm, n, dim, vp(d_members_ptr),
+        nmembers, hp(seg_starts), hp(seg_sizes), hp(ncenters),
+        seg_starts.size, vp(d_centers_ptr), kmax, vp(d_prev_counts_ptr),
+        vp(d_lambdas_ptr), 1 if update else 0, vp(d_labels_ptr),
+        vp(d_dists_ptr), vp(d_counts_ptr), vp(d_cluster_idx_ptr),
+        vp(d_cluster_dist_ptr), vp(d_sums_ptr))
+    if rc != 0:
+        raise SptagAmdError(rc, "kmeans_assign_device")
 
 
 def merge_topk(vids, dists, vid_base, k, device=0):

@@ -150,17 +150,163 @@ def _kmeans_split(xf, members, K, iters=8, sample=4096, gen=None):
     return groups, reps
 
 
+def _check_kmeans(kmeans):
+    if kmeans not in ("torch", "hip"):
+        raise ValueError(f'kmeans must be "torch" or "hip", got {kmeans!r}')
+
+
+def _bkt_split_levels_hip(xf, kmeans_k, big_cluster, gen, cent, cs, ce, small,
+                          iters=8, sample=4096, verbose=False):
+    """Phase A of build_bkt_tree by the k-means-assign HIP kernels
+    (sptag_amd.kmeans_assign_device), level by level: the open clusters of a
+    level are the segments of one member list. Every cluster draws a random
+    order of its members from the generator; the first `sample` of it are its
+    sample and the first K of those its initial centers. A Lloyd iteration is
+    one update=1 call over the sampled segments (next centers sums / counts,
+    an empty center keeps its row), the final assignment one update=0 call
+    over the full segments, whose cluster_idx is each child's representative:
+    its nearest member, the last such in member order. The children are
+    carved with one segmented sort by label. The host sees counts and
+    representatives once per level. Appends to cent / cs / ce / small as
+    the stack loop does."""
+    from . import kmeans_assign_device, VT_FLOAT, DM_L2
+    dev = xf.device
+    n, d = xf.shape
+    xf = xf.contiguous()
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+
+    def assign(members, starts, sizes, centers, ncent, update, outs):
+        torch.cuda.synchronize(dev)     # the library runs on the default stream
+        kmeans_assign_device(
+            xf.data_ptr(), VT_FLOAT, DM_L2, n, d, members.data_ptr(),
+            members.numel(), i32(starts), i32(sizes), ncent,
+            centers.data_ptr(), kmeans_k, None, None, update,
+            *[None if t is None else t.data_ptr() for t in outs],
+            device=dev.index or 0)
+
+    perm = torch.arange(n, device=dev)      # the open clusters' members, cluster by cluster
+    nodes, sizes = [0], np.array([n], dtype=np.int64)
+    while nodes:
+        S, total = len(nodes), int(sizes.sum())
+        K = i32(np.minimum(kmeans_k, np.maximum(2, sizes // 8)))
+        starts = _seg_starts(sizes)
+        szt = torch.as_tensor(sizes, device=dev)
+        seg = torch.repeat_interleave(torch.arange(S, device=dev), szt)
+        # a random order inside every cluster; its head is the sample
+        order = _segmented_order(
+            torch.rand(total, generator=gen, device=dev), seg)
+        smp = perm[order][_pos_in_segment(seg, szt) < sample].to(torch.int32)
+        ssz = np.minimum(sizes, sample)
+        sst = _seg_starts(ssz)
+        kk = torch.arange(kmeans_k, device=dev)[None, :]
+        cpos = (torch.as_tensor(sst, device=dev)[:, None]
+                + torch.minimum(kk, torch.as_tensor(K, device=dev)[:, None] - 1))
+        centers = xf[smp[cpos].long()].contiguous()        # [S, kmeans_k, d]
+        # rows at or past K[s] are never read or written: they stay zero
+        counts = torch.zeros((S, kmeans_k), dtype=torch.int32, device=dev)
+        cidx = torch.zeros_like(counts)
+        cdist = torch.zeros((S, kmeans_k), device=dev)
+        sums = torch.zeros((S, kmeans_k, d), device=dev)
+        lab = torch.empty(smp.numel(), dtype=torch.int32, device=dev)
+        for _ in range(iters):
+            assign(smp, sst, ssz, centers, K, 1,
+                   (lab, None, counts, cidx, cdist, sums))
+            newc = sums / counts.clamp(min=1)[:, :, None].float()
+            centers = torch.where((counts > 0)[:, :, None], newc,
+                                  centers).contiguous()
+        del smp, lab, sums
+        lab = torch.empty(total, dtype=torch.int32, device=dev)
+        assign(perm.to(torch.int32), starts, sizes, centers, K, 0,
+               (lab, None, counts, cidx, cdist, None))
+        cnt_np, rep_np = counts.cpu().numpy(), cidx.cpu().numpy()
+        perm = perm[_segmented_order(lab, seg, stable=True)]   # label-sorted clusters
+        del lab, order, seg
+
+        child_sz, child_big, fb_pos, fb_slot, next_nodes = [], [], [], [], []
+        for s in range(S):
+            m, k = int(sizes[s]), int(K[s])
+            nz = np.nonzero(cnt_np[s, :k])[0]
+            if len(nz) > 1:
+                csz, reps = cnt_np[s, nz], rep_np[s, nz]
+            else:       # degenerate split: even groups in member order
+                per = (m + k - 1) // k
+                csz, reps = np.diff(np.append(np.arange(0, m, per), m)), None
+            cs[nodes[s]] = len(cent)
+            a = int(starts[s])
+            for j, z in enumerate(csz):
+                child, z = len(cent), int(z)
+                if reps is None:        # the group's first member, read below
+                    fb_pos.append(a)
+                    fb_slot.append(child)
+                cent.append(-1 if reps is None else int(reps[j]))
+                cs.append(-1)
+                ce.append(-1)
+                if z > big_cluster:
+                    next_nodes.append(child)
+                elif z > 1:
+                    small.append((child, perm[a:a + z]))
+                child_sz.append(z)
+                child_big.append(z > big_cluster)
+                a += z
+            ce[nodes[s]] = len(cent)
+        if fb_pos:
+            first = perm[torch.as_tensor(fb_pos, device=dev)].cpu().numpy()
+            for slot, v in zip(fb_slot, first):
+                cent[slot] = int(v)
+        child_sz, child_big = np.array(child_sz), np.array(child_big)
+        perm = perm[torch.repeat_interleave(
+            torch.as_tensor(child_big, device=dev),
+            torch.as_tensor(child_sz, device=dev))]
+        nodes, sizes = next_nodes, child_sz[child_big].astype(np.int64)
+        if verbose:
+            print(f"  bkt phase A: {len(cent)} nodes, {len(nodes)} open clusters")
+
+
+def _segment_sums_hip(xf, members, sizes):
+    """[len(sizes), d] sums of the vectors of consecutive segments of
+    `members`, by the k-means-assign kernels with one center a segment: the
+    same bytes on every run."""
+    from . import kmeans_assign_device, VT_FLOAT, DM_L2
+    dev, (n, d), S = xf.device, xf.shape, len(sizes)
+    xf = xf.contiguous()
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+    members = members.to(torch.int32).contiguous()
+    centers = torch.zeros((S, 1, d), device=dev)
+    lab = torch.empty(members.numel(), dtype=torch.int32, device=dev)
+    cnt = torch.empty((3, S), dtype=torch.int32, device=dev)
+    sums = torch.empty((S, 1, d), device=dev)
+    torch.cuda.synchronize(dev)     # the library runs on the default stream
+    kmeans_assign_device(
+        xf.data_ptr(), VT_FLOAT, DM_L2, n, d, members.data_ptr(),
+        members.numel(), _seg_starts(sizes).astype(np.int32), sizes,
+        np.ones(S, dtype=np.int32), centers.data_ptr(), 1, None, None, 1,
+        lab.data_ptr(), None, cnt[0].data_ptr(), cnt[1].data_ptr(),
+        cnt[2].data_ptr(), sums.data_ptr(), device=dev.index or 0)
+    return sums[:, 0]
+
+
 def build_bkt_tree(vectors, *, kmeans_k=32, leaf_size=32, big_cluster=4096,
-                   seed=2016, device=None, verbose=False):
+                   seed=2016, device=None, verbose=False, kmeans="torch"):
     """Returns (tree_start int32[ntrees], tree_nodes int32[N,3]) in the
     reference layout (BKTree.h:25 BKTNode {centerid,childStart,childEnd},
-    children contiguous, childEnd exclusive, leaves childStart=-1)."""
+    children contiguous, childEnd exclusive, leaves childStart=-1).
+    kmeans: "torch" (one cluster at a time, cdist + argmin) or "hip" (level
+    by level on the k-means-assign kernels; GPU only, kmeans_k <= 64) for the
+    splits of the clusters above big_cluster."""
+    _check_kmeans(kmeans)
     device, xf, gen = _prologue(vectors, device, seed)
+    if kmeans == "hip" and xf.device.type != "cuda":
+        raise RuntimeError('kmeans="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
     n = xf.shape[0]
 
     cent, cs, ce = [n], [-1], [-1]   # root: centerid=n (unused; as reference)
     small = []                        # (node_idx, members) clusters <= big_cluster
     stack = [(0, torch.arange(n, device=device, dtype=torch.int64))]
+    if kmeans == "hip":
+        stack = []
+        _bkt_split_levels_hip(xf, kmeans_k, big_cluster, gen, cent, cs, ce,
+                              small, verbose=verbose)
     while stack:
         node, members = stack.pop()
         groups, reps = _kmeans_split(xf, members, kmeans_k, gen=gen)
@@ -196,8 +342,13 @@ def build_bkt_tree(vectors, *, kmeans_k=32, leaf_size=32, big_cluster=4096,
             torch.arange(len(small), device=device), sizes_t)
         # order members within each cluster by distance to its centroid
         pts = xf[members_all]
-        cen = torch.zeros((len(small), pts.shape[1]), device=device)
-        cen.index_add_(0, cl_of, pts)
+        if kmeans == "hip":
+            # index_add_ adds with floating-point atomics, in an order that
+            # changes from run to run: the kernel's sums do not
+            cen = _segment_sums_hip(xf, members_all, [g.numel() for _, g in small])
+        else:
+            cen = torch.zeros((len(small), pts.shape[1]), device=device)
+            cen.index_add_(0, cl_of, pts)
         cen = cen / sizes_t[:, None].float()
         dcent = ((pts - cen[cl_of]) ** 2).sum(1)
         # cluster-major, dist-ordered
@@ -955,14 +1106,16 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
                        srefine_k=512, srefine_mc=8192, fill_pruned=False,
                        seed=2016, device=None, normalized=False,
                        verbose=False, leaf_knn="torch", prune="torch",
-                       join="torch"):
+                       join="torch", kmeans="torch"):
     """Full build: returns dict(vectors, tree_start, tree_nodes, graph) ready
     for AnnIndex.FromArrays (vectors already cosine-normalized when needed,
     as the reference stores them on disk). prune: "torch" or "hip" (GPU
     only), the RebuildNeighbors step of every graph stage; join: likewise,
-    the step that grows the candidate pools."""
+    the step that grows the candidate pools; kmeans: likewise, the cluster
+    splits of the BKT tree."""
     _prune_fn(prune)
     _join_fn(join)
+    _check_kmeans(kmeans)
     if not normalized:
         vectors = normalize_base(vectors, distmethod)
     if algo == "KDT":
@@ -971,7 +1124,7 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
     else:
         tree_start, tree_nodes = build_bkt_tree(
             vectors, kmeans_k=kmeans_k, leaf_size=leaf_size, seed=seed,
-            device=device, verbose=verbose)
+            device=device, verbose=verbose, kmeans=kmeans)
     if verbose:
         print(f"  {algo} tree: {len(tree_nodes)} nodes")
     graph, cids, cdst = build_rng_graph(

@@ -249,6 +249,44 @@ int launch_pool_join(int valuetype, int distmethod, const void* vectors, int32_t
                      const float* new_dists, int32_t nnew, int32_t kout, int32_t* out_ids,
                      float* out_dists);
 
+/* K-means assign (exact.hip): one KmeansAssign pass over many segments.
+ * Segment s is members[seg.start : seg.start + size], its centers rows
+ * [s][0..ncenters) of centers ([nseg][kmax][dim], the vectors' value type). A
+ * workgroup owns one KmItem: `count` consecutive members of one segment from
+ * members[start] on, whose first is position pos0 of the segment; count is at
+ * most KMEANS_ITEM_MAX and items of a segment are
+ * consecutive in the list, in member order (segs[s].item0, nitems). Every
+ * member is settled by the rule of include/sptag_amd.h; counts, extremes and
+ * sums are written for centers below ncenters only. keys ([nseg][kmax]) and
+ * partials (update only: [nitems][kmax][dim] dwords) are scratch. All
+ * pointers are device memory; every member is inside the vectors. */
+enum { KMEANS_MAX_K = 64, KMEANS_ITEM_MAX = 1024 };
+struct KmItem { int32_t seg, start, count, pos0; };
+struct KmSeg { int32_t ncenters, item0, nitems; };
+struct KmArgs {
+    const int32_t* members;
+    const KmItem* items;
+    const KmSeg* segs;
+    const void* centers;
+    const int32_t* prev_counts;   /* [nseg][kmax], null with lambdas */
+    const float* lambdas;         /* [nseg] or null: no penalty */
+    int32_t nseg, nitems, kmax, update;
+    int32_t* out_labels;
+    float* out_dists;             /* may be null */
+    int32_t* out_counts;
+    int32_t* out_cluster_idx;
+    float* out_cluster_dist;
+    float* out_sums;              /* update only */
+    unsigned long long* keys;
+    void* partials;
+};
+/* members of a tile for the value type, and how many tiles an item may hold
+ * when the call has ntiles of them in all */
+int kmeans_assign_tile(int valuetype);
+int kmeans_assign_item_tiles(int valuetype, int64_t ntiles);
+int launch_kmeans_assign(int valuetype, int distmethod, const void* vectors, int32_t dim,
+                         const KmArgs& args);
+
 /* heap probe (tests/test_gpu_heap_ops.py): a script of nops heap operations
  * (ops[i] != 0: insert {nodes[i], dists[i]}; 0: pop) on a heap of capacity
  * `cap` whose entries [0..lsplit] sit in LDS (lsplit 0: none), run once with

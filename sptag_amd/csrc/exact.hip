@@ -1964,6 +1964,543 @@ void pool_join_i8_kernel(const int8_t* __restrict__ vectors, int d,
 }
 
 /* ------------------------------------------------------------------ *
+ * K-means assign: segmented nearest-center step
+ * ------------------------------------------------------------------ *
+ * Segment s has a slice of the member list and at most 64 centers of its own.
+ * A workgroup owns one KmItem, a run of consecutive members of one segment,
+ * and walks it in tiles. The centers are the LDS-resident side, the "query
+ * tile" of the kernels above (32 slots, or 64 for kmax > 32); a member's
+ * vector is gathered from global memory once, into LDS, and serves the
+ * distances and then the sums.
+ *
+ *   dists   f32: tiles of 16 members, the micro-tiles and the reference-order
+ *           fold of the kernels above. RES: centers and tile whole in LDS,
+ *           the next tile's loads in flight in registers during the math.
+ *           Otherwise (large dims) centers and tile stream through LDS in
+ *           slabs of FKS columns with the accumulators kept, the next slab's
+ *           loads in flight.
+ *           int8: tiles of 64 members, one 32x32 MFMA block per wave (two
+ *           member blocks x one or two center blocks), everything resident.
+ *   choose  The tile's distances go through LDS as [member][center]; a wave
+ *           takes a member at a time, lane k adds center k's penalty (an f32
+ *           product and an f32 sum, each rounded once) and a butterfly over
+ *           (dist, k) keeps the smallest qualifying distance, the lowest k
+ *           among equals: the serial rule's answer.
+ *   counts  Per item in LDS, then one integer atomic per center.
+ *   extreme A 64-bit key (order-preserving f32 bits, -0 folded to +0, above
+ *           the complemented position) goes through an LDS atomic max
+ *           (update) or min, then one global atomic per center and item: the
+ *           largest distance at the smallest position, or the smallest
+ *           distance at the largest position, whatever the arrival order.
+ *   sums    The item's sums live in LDS as [center][column], a thread owning
+ *           its columns and adding the members in order: no atomics. Where
+ *           every column fits beside the resident tile they are added tile
+ *           by tile from LDS, the one read serving both. Where they do not
+ *           (the streaming f32 form; int8 with kmax > 32 and d > 48) the
+ *           item's labels stay in LDS and its vectors are read a second
+ *           time after the last tile, a slab of columns at a time. Each
+ *           item writes its partial; kmeans_finish_kernel adds the partials
+ *           of a segment in list order (int8: as 64-bit integers, rounded
+ *           once), so equal calls give equal bytes. */
+
+enum { KM_MAX_K = KMEANS_MAX_K, KM_ITEM_MAX = KMEANS_ITEM_MAX, KM_IT = 64, KM_DS = KM_MAX_K + 1,
+       KM_PF = 8, KM_ITEMS_TARGET = 2048, KM_LDS_MAX = RP_LDS_MAX };
+static_assert(KM_MAX_K == 2 * XQT && KM_IT == 2 * RI_T, "two query tiles, two MFMA blocks");
+
+struct KmLds { uint32_t ext, cnt, aux, lab, dmat, cen, tile, sums, total; int ss; };
+
+/* cen_words / tile_words: dwords of the centers and of a tile (or of their
+ * slabs), trows: members of a tile. ss: columns of the sums that fit (a
+ * multiple of 4, at most the padded dim; 0 without update). */
+static inline __host__ __device__ KmLds km_lds(uint32_t cen_words, uint32_t tile_words,
+                                               int trows, int kmax, int d, int update)
+{
+    KmLds l;
+    uint32_t b = 0;
+    l.ext = b;  b += KM_MAX_K * 8;
+    l.cnt = b;  b += KM_MAX_K * 4;
+    l.aux = b;  b += (KM_MAX_K + 2 * KM_IT) * 4;   /* int8: center self-dots, tile ids */
+    l.lab = b;  b += KM_ITEM_MAX;
+    l.dmat = b; b += (uint32_t)trows * KM_DS * 4;
+    b = (b + 15) & ~15u;
+    l.cen = b;  b += cen_words * 4;
+    b = (b + 15) & ~15u;
+    l.tile = b; b += tile_words * 4;
+    b = (b + 15) & ~15u;
+    l.sums = b;
+    l.ss = 0;
+    if (update && b < KM_LDS_MAX) {
+        const int room = (int)((KM_LDS_MAX - b) / ((uint32_t)kmax * 4)) & ~3;
+        const int dp = (d + 3) & ~3;
+        l.ss = room < dp ? room : dp;
+    }
+    b += (uint32_t)l.ss * kmax * 4;
+    l.total = b;
+    return l;
+}
+
+static inline __host__ __device__ KmLds km_f32_lds(int d, int nqt, int kmax, int update, bool res)
+{
+    const int qs = res ? f32_qstride(d) : FQSS;
+    return km_lds((uint32_t)(nqt * XQT * qs), (uint32_t)(FRT * qs), FRT, kmax, d, update);
+}
+
+/* whether the f32 kernel keeps the centers and a tile whole, and with update
+ * every column of the sums beside them */
+static inline __host__ __device__ bool km_f32_resident(int d, int nqt, int kmax, int update)
+{
+    if (f32_qstride(d) > FQRES_MAX) return false;
+    const KmLds l = km_f32_lds(d, nqt, kmax, update, true);
+    return l.total <= KM_LDS_MAX && (!update || l.ss >= d);
+}
+
+static inline __host__ __device__ KmLds km_i8_lds(int d, int ncb, int kmax, int update)
+{
+    const uint32_t wl = (uint32_t)((d + 3) >> 2) | 1;
+    return km_lds(ncb * XQT * wl, KM_IT * wl, KM_IT, kmax, d, update);
+}
+
+struct KmCtx {
+    unsigned long long* ext;    /* LDS [KM_MAX_K] */
+    int* cnt;                   /* LDS [KM_MAX_K] */
+    uint8_t* lab;               /* LDS [KM_ITEM_MAX]: the labels of the item's members */
+    float* dmat;                /* LDS [tile rows][KM_DS] */
+    int nc;
+    bool haspen;
+    float pen;                  /* lane k: lambda * prev_counts[k] */
+};
+
+/* Empty counts and extremes, this lane's penalty. Ends with a barrier. */
+DEV KmCtx km_begin(unsigned char* lds, const KmLds& L, const KmArgs& A, const KmItem& it, int nc)
+{
+    KmCtx c;
+    c.ext = (unsigned long long*)(lds + L.ext);
+    c.cnt = (int*)(lds + L.cnt);
+    c.lab = lds + L.lab;
+    c.dmat = (float*)(lds + L.dmat);
+    c.nc = nc;
+    c.haspen = A.lambdas != nullptr;
+    c.pen = 0.0f;
+    const int lane = threadIdx.x & 63;
+    if (c.haspen && lane < nc)
+        c.pen = __fmul_rn(A.lambdas[it.seg], (float)A.prev_counts[(size_t)it.seg * A.kmax + lane]);
+    if (threadIdx.x < KM_MAX_K) {
+        c.cnt[threadIdx.x] = 0;
+        c.ext[threadIdx.x] = A.update ? 0ull : ~0ull;
+    }
+    uint32_t* sums = (uint32_t*)(lds + L.sums);
+    for (int i = threadIdx.x; i < L.ss * A.kmax; i += blockDim.x) sums[i] = 0u;
+    __syncthreads();
+    return c;
+}
+
+/* One wave settles rows [row0, row0 + nrows) of dmat; row r is member m0 + r
+ * of the item. Lane k speaks for center k. */
+DEV void km_choose(const KmCtx& c, const KmArgs& A, const KmItem& it, int row0, int nrows, int m0)
+{
+    const int lane = threadIdx.x & 63;
+    for (int r = row0; r < row0 + nrows && m0 + r < it.count; r++) {
+        float v = c.dmat[r * KM_DS + lane];
+        if (c.haspen) v = __fadd_rn(v, c.pen);
+        const bool ok = lane < c.nc && v > -MAXDIST && v < MAXDIST;
+        float bv = ok ? v : MAXDIST;
+        int bk = ok ? lane : (int)KM_MAX_K;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int ok2 = __shfl_xor(bk, o);
+            if (ov < bv || (ov == bv && ok2 < bk)) { bv = ov; bk = ok2; }
+        }
+        if (bk == KM_MAX_K) bk = 0;     /* no center qualifies: label 0 at MaxDist */
+        if (lane == 0) {
+            const int mi = m0 + r;
+            A.out_labels[(size_t)it.start + mi] = bk;
+            if (A.out_dists) A.out_dists[(size_t)it.start + mi] = bv;
+            c.lab[mi] = (uint8_t)bk;
+            atomicAdd(&c.cnt[bk], 1);
+            const unsigned long long key = pj_pack(bv, (int32_t)~(uint32_t)(it.pos0 + mi));
+            if (A.update) atomicMax(&c.ext[bk], key);
+            else atomicMin(&c.ext[bk], key);
+        }
+    }
+}
+
+/* the item's counts and extremes to the segment's. Starts with a barrier. */
+DEV void km_end(const KmCtx& c, const KmArgs& A, const KmItem& it)
+{
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < c.nc && c.cnt[k] > 0) {
+        const size_t at = (size_t)it.seg * A.kmax + k;
+        atomicAdd(&A.out_counts[at], c.cnt[k]);
+        if (A.update) atomicMax(&A.keys[at], c.ext[k]);
+        else atomicMin(&A.keys[at], c.ext[k]);
+    }
+}
+
+/* columns [0, ncol) of the sums += members m0 .. m0 + nm - 1 of the item, in
+ * that order; src(mi, c): column c of member mi. A thread owns its columns. */
+template <class ACC, class SRC>
+DEV void km_accumulate(ACC* sums, int ss, const uint8_t* lab, int m0, int nm, int ncol, SRC src)
+{
+    for (int c = threadIdx.x; c < ncol; c += blockDim.x)
+        for (int m = 0; m < nm; m += KM_PF) {
+            ACC v[KM_PF];
+#pragma unroll
+            for (int j = 0; j < KM_PF; j++) v[j] = m + j < nm ? src(m0 + m + j, c) : (ACC)0;
+#pragma unroll
+            for (int j = 0; j < KM_PF; j++)
+                if (m + j < nm) sums[lab[m0 + m + j] * ss + c] += v[j];
+        }
+}
+
+/* columns [0, ncol) of the sums to `part` (the item's partial at the slab's
+ * first column), and cleared. Barriers before and after. */
+template <class ACC>
+DEV void km_flush_sums(ACC* sums, int ss, int nc, int ncol, ACC* __restrict__ part, int d)
+{
+    __syncthreads();
+    for (int i = threadIdx.x; i < nc * ncol; i += blockDim.x) {
+        const int k = i / ncol, c = i - k * ncol;
+        part[(size_t)k * d + c] = sums[k * ss + c];
+        sums[k * ss + c] = (ACC)0;
+    }
+    __syncthreads();
+}
+
+/* the sums of a resident tile (members m0 .. m0 + nm - 1, `last`: the item's
+ * last); every column fits (ss >= d). Ends with a barrier. */
+template <class ACC, class SRC>
+DEV void km_tile_sums(ACC* sums, int ss, const KmCtx& c, int m0, int nm, bool last, int d,
+                      ACC* __restrict__ part, SRC src)
+{
+    km_accumulate(sums, ss, c.lab, m0, nm, d, src);
+    if (last) km_flush_sums(sums, ss, c.nc, d, part, d);
+    else __syncthreads();
+}
+
+/* the sums of the whole item after its last tile, a slab of ss columns at a
+ * time, from the labels in LDS; src(mi, c) reads the vectors again */
+template <class ACC, class SRC>
+DEV void km_item_sums(ACC* sums, int ss, const KmCtx& c, int count, int d,
+                      ACC* __restrict__ part, SRC src)
+{
+    for (int c0 = 0; c0 < d; c0 += ss) {
+        const int ncol = min(ss, d - c0);
+        km_accumulate(sums, ss, c.lab, 0, count, ncol,
+                      [&](int mi, int col) { return src(mi, c0 + col); });
+        km_flush_sums(sums, ss, c.nc, ncol, part + c0, d);
+    }
+}
+
+__global__ __launch_bounds__(256)
+void kmeans_init_kernel(KmArgs A)
+{
+    const size_t total = (size_t)A.nseg * A.kmax;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * 256) {
+        if ((int)(i % A.kmax) >= A.segs[i / A.kmax].ncenters) continue;
+        A.out_counts[i] = 0;
+        A.keys[i] = A.update ? 0ull : ~0ull;
+    }
+}
+
+/* block (s, y): the extremes of segment s (y == 0) and columns of its sums */
+template <bool I8>
+__global__ __launch_bounds__(256)
+void kmeans_finish_kernel(KmArgs A, int d)
+{
+    const int s = blockIdx.x;
+    const KmSeg sg = A.segs[s];
+    const size_t at = (size_t)s * A.kmax;
+    if (blockIdx.y == 0 && (int)threadIdx.x < sg.ncenters) {
+        const int k = threadIdx.x;
+        const bool any = A.out_counts[at + k] > 0;
+        const unsigned long long key = A.keys[at + k];
+        /* the key's low word is the complemented position in the segment */
+        const size_t first = sg.nitems > 0 ? (size_t)A.items[sg.item0].start : 0;
+        A.out_cluster_idx[at + k] = any ? A.members[first + (uint32_t)~(uint32_t)key] : -1;
+        A.out_cluster_dist[at + k] = any ? pj_unpack_dist(key) : (A.update ? -MAXDIST : MAXDIST);
+    }
+    if (!A.update) return;
+    const int i = blockIdx.y * 256 + threadIdx.x;
+    if (i >= sg.ncenters * d) return;
+    const size_t stride = (size_t)A.kmax * d;
+    if (I8) {
+        const int32_t* p = (const int32_t*)A.partials + (size_t)sg.item0 * stride + i;
+        long long acc = 0;
+        for (int j = 0; j < sg.nitems; j++) acc += p[j * stride];
+        A.out_sums[at * d + i] = (float)acc;
+    } else {
+        const float* p = (const float*)A.partials + (size_t)sg.item0 * stride + i;
+        float acc = 0.0f;
+        for (int j = 0; j < sg.nitems; j++) acc += p[j * stride];
+        A.out_sums[at * d + i] = acc;
+    }
+}
+
+/* NQT: query tiles of 32 center slots (2 for kmax > 32) */
+template <int DM, bool RES, int NQT>
+__global__ __launch_bounds__(XTHREADS)
+void kmeans_f32_kernel(const float* __restrict__ vectors, int d, KmArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const int qs = RES ? f32_qstride(d) : FQSS;     /* row stride of both buffers */
+    const KmLds L = km_f32_lds(d, NQT, A.kmax, A.update, RES);
+    float* cbuf = (float*)(xlds + L.cen);       /* the centers (or their slab) */
+    float* tbuf = (float*)(xlds + L.tile);      /* the tile's vectors (or their slab) */
+    float* sums = (float*)(xlds + L.sums);
+    const int tid = threadIdx.x;
+    const int g = tid & 15, gq = (tid >> 4) & 3, gr = tid >> 6, lr = tid >> 4;
+    const KmItem it = A.items[blockIdx.x];
+    const int nc = A.segs[it.seg].ncenters;
+    const float* cen = (const float*)A.centers + (size_t)it.seg * A.kmax * d;
+    const int32_t* mem = A.members + it.start;
+    float* part = A.update ? (float*)A.partials + (size_t)blockIdx.x * A.kmax * d : nullptr;
+    const bool vec = (d & 3) == 0 && ((uintptr_t)vectors & 15) == 0;
+    const bool vecc = (d & 3) == 0 && ((uintptr_t)A.centers & 15) == 0;
+    const bool two = NQT == 2 && nc > XQT;      /* the second center tile is in use */
+    const KmCtx ctx = km_begin(xlds, L, A, it, nc);
+
+    const int nslab = (d + FKS - 1) / FKS;
+    const int ntile = (it.count + FRT - 1) / FRT;   /* >= 1: an item is not empty */
+    /* the vector of member lr of tile t, null past the item's end */
+    auto row_of = [&](int32_t id) { return id >= 0 ? vectors + (size_t)id * d : nullptr; };
+    auto tile_id = [&](int t) { return t * FRT + lr < it.count ? mem[t * FRT + lr] : -1; };
+    float a0[FMQ][FMR], a1[FMQ][FMR];
+    /* after a tile's last slab: the distances to LDS, the members settled */
+    auto settle = [&](int t, const float* qa, const float* rb, int slab) {
+        float d0[FMQ], d1[FMQ] = {};
+        rp_fold<DM, FMQ>(a0, qa, rb, qs, qs, slab, d, g, d0);
+        if (two) rp_fold<DM, FMQ>(a1, qa + XQT * qs, rb, qs, qs, slab, d, g, d1);
+        if (g < FMR) {      /* member gr*4 + g of the tile against centers gq + 4*i (+ 32) */
+            float* row = ctx.dmat + (gr * FMR + g) * KM_DS;
+#pragma unroll
+            for (int i = 0; i < FMQ; i++) {
+                row[gq + 4 * i] = d0[i];
+                if (NQT == 2) row[XQT + gq + 4 * i] = d1[i];
+            }
+        }
+        __syncthreads();
+        km_choose(ctx, A, it, gr * FMR, FMR, t * FRT);
+        __syncthreads();
+    };
+
+    if constexpr (RES) {
+        for (int i = tid; i < NQT * XQT * qs; i += XTHREADS) {
+            const int r = i / qs, c = i - r * qs;
+            cbuf[i] = (r < nc && c < d) ? cen[(size_t)r * d + c] : 0.0f;
+        }
+        /* this thread's columns 4*(g + 16*k) of row lr of a tile */
+        float4 pre[FQRES_MAX / 64];
+        auto tile_load = [&](int32_t id) {
+            const float* p = row_of(id);
+#pragma unroll
+            for (int k = 0; k < FQRES_MAX / 64; k++) {
+                const int col = 4 * (g + 16 * k);
+                if (col < qs) pre[k] = rp_cols4(p, d, col, vec);
+            }
+        };
+        auto tile_store = [&]() {
+#pragma unroll
+            for (int k = 0; k < FQRES_MAX / 64; k++) {
+                const int col = 4 * (g + 16 * k);
+                if (col < qs) *(float4*)(tbuf + lr * qs + col) = pre[k];
+            }
+        };
+        int32_t idn = tile_id(1);       /* ids are read a tile ahead of their vectors */
+        tile_load(tile_id(0));
+        tile_store();
+        __syncthreads();
+        for (int t = 0; t < ntile; t++) {
+            if (t + 1 < ntile) {        /* in flight while this tile computes */
+                tile_load(idn);
+                idn = tile_id(t + 2);
+            }
+            for (int slab = 0; slab < nslab; slab++) {
+                const float* qa = cbuf + gq * qs + slab * FKS;
+                const float* rb = tbuf + gr * FMR * qs + slab * FKS;
+                rp_math<DM, FMQ>(a0, qa, rb, qs, qs, slab, d, g);
+                if (two) rp_math<DM, FMQ>(a1, qa + XQT * qs, rb, qs, qs, slab, d, g);
+                if (slab == nslab - 1) settle(t, qa, rb, slab);
+            }
+            if (A.update)
+                km_tile_sums(sums, L.ss, ctx, t * FRT, min((int)FRT, it.count - t * FRT),
+                             t + 1 == ntile, d, part,
+                             [&](int mi, int c) { return tbuf[(mi - t * FRT) * qs + c]; });
+            if (t + 1 < ntile) {
+                tile_store();
+                __syncthreads();
+            }
+        }
+    } else {
+        /* step st is slab st % nslab of tile st / nslab; this thread's columns
+         * of member lr and of centers lr + 16*q */
+        float4 pr, pc[NQT * 2];
+        auto slab_load = [&](int st) {
+            const int t = st / nslab, k0 = (st - t * nslab) * FKS;
+            pr = f32_cols_load(row_of(tile_id(t)), d, k0, vec);
+#pragma unroll
+            for (int q = 0; q < NQT * 2; q++) {
+                const int k = q * 16 + lr;
+                pc[q] = f32_cols_load(k < nc ? cen + (size_t)k * d : nullptr, d, k0, vecc);
+            }
+        };
+        const int nstep = ntile * nslab;
+        slab_load(0);
+        for (int st = 0; st < nstep; st++) {
+            const int t = st / nslab, slab = st - t * nslab;
+            f32_slab_store(tbuf, FQSS, pr);
+#pragma unroll
+            for (int q = 0; q < NQT * 2; q++) f32_slab_store(cbuf, FQSS, pc[q], q * 16);
+            __syncthreads();
+            if (st + 1 < nstep) slab_load(st + 1);      /* in flight during the math */
+            const float* qa = cbuf + gq * qs;
+            const float* rb = tbuf + gr * FMR * qs;
+            rp_math<DM, FMQ>(a0, qa, rb, qs, qs, slab, d, g);
+            if (two) rp_math<DM, FMQ>(a1, qa + XQT * qs, rb, qs, qs, slab, d, g);
+            if (slab == nslab - 1) settle(t, qa, rb, slab);
+            __syncthreads();    /* the slab is free */
+        }
+        if (A.update) {
+            __syncthreads();
+            km_item_sums(sums, L.ss, ctx, it.count, d, part,
+                         [&](int mi, int c) { return vectors[(size_t)mem[mi] * d + c]; });
+        }
+    }
+    km_end(ctx, A, it);
+}
+
+/* NCB: 32-center MFMA blocks (2 for kmax > 32); 64 * 2 * NCB threads */
+template <int DM, int NCB>
+__global__ __launch_bounds__(128 * NCB)
+void kmeans_i8_kernel(const int8_t* __restrict__ vectors, int d, KmArgs A)
+{
+    enum { NT = 128 * NCB, NP = (KM_IT * I_MAX_W + NT - 1) / NT, RPW = KM_IT / (2 * NCB) };
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const int W = (d + 3) >> 2, WL = W | 1;
+    const KmLds L = km_i8_lds(d, NCB, A.kmax, A.update);
+    uint32_t* cl = (uint32_t*)(xlds + L.cen);       /* [NCB * 32][WL] the centers */
+    uint32_t* tl = (uint32_t*)(xlds + L.tile);      /* [KM_IT][WL] the tile's vectors */
+    int* caa = (int*)(xlds + L.aux);                /* the centers' self-dots */
+    int32_t* mids = caa + KM_MAX_K;                 /* [2][KM_IT], by tile parity */
+    int* sums = (int*)(xlds + L.sums);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mb = wave & 1, cb = wave >> 1, h = lane >> 5, col = lane & 31;
+    const KmItem it = A.items[blockIdx.x];
+    const int nc = A.segs[it.seg].ncenters;
+    const int8_t* cen = (const int8_t*)A.centers + (size_t)it.seg * A.kmax * d;
+    const int32_t* mem = A.members + it.start;
+    int* part = A.update ? (int*)A.partials + (size_t)blockIdx.x * A.kmax * d : nullptr;
+    /* whole dwords to a row, dword aligned: loaded into registers a tile
+     * ahead; other pitches are packed from bytes at the store */
+    const bool wide = (d & 3) == 0 && ((uintptr_t)vectors & 3) == 0;
+    const bool widec = (d & 3) == 0 && ((uintptr_t)A.centers & 3) == 0;
+
+    for (int i = tid; i < NCB * XQT * W; i += NT) {
+        const int r = i / W, w = i - r * W;
+        uint32_t v = 0;
+        if (r < nc)
+            v = widec ? *(const uint32_t*)(cen + (size_t)r * d + 4 * w) : i8_pack_dword(cen, r, w, d);
+        cl[r * WL + w] = v;
+    }
+    /* the member of row tid of tile t, -1 past the item's end */
+    auto tile_id = [&](int t) {
+        const int ri = t * KM_IT + tid;
+        return (tid < KM_IT && ri < it.count) ? mem[ri] : -1;
+    };
+    if (tid < KM_IT) {
+        mids[tid] = tile_id(0);
+        mids[KM_IT + tid] = tile_id(1);
+    }
+    int32_t idn = tile_id(2);           /* ids are read two tiles ahead of their use */
+    const KmCtx ctx = km_begin(xlds, L, A, it, nc);
+    if (tid < KM_MAX_K) {
+        int s = 0;
+        if (tid < NCB * XQT)
+            for (int w = 0; w < W; w++) {
+                const int v = (int)cl[tid * WL + w];
+                s = __builtin_amdgcn_sdot4(v, v, s, false);
+            }
+        caa[tid] = s;
+    }
+
+    /* dword j of this thread is dword w of row r of the tile, with
+     * r * W + w = tid + j * NT; (r0, w0) is the first */
+    const int r0 = tid / W, w0 = tid - r0 * W, dr = NT / W, dw = NT - dr * W;
+    uint32_t pre[NP];
+    auto stage_load = [&](int t) {
+        if (!wide) return;
+        const int32_t* ids = mids + (t & 1) * KM_IT;
+        int r = r0, w = w0;
+#pragma unroll
+        for (int j = 0; j < NP; j++) {
+            const int32_t id = r < KM_IT ? ids[r] : -1;
+            pre[j] = id >= 0 ? ((const uint32_t*)(vectors + (size_t)id * d))[w] : 0u;
+            r += dr;
+            w += dw;
+            if (w >= W) { w -= W; r++; }
+        }
+    };
+    auto stage_store = [&](int t) {
+        if (!wide) {
+            const int32_t* ids = mids + (t & 1) * KM_IT;
+            for (int i = tid; i < KM_IT * W; i += NT) {
+                const int r = i / W, w = i - r * W;
+                tl[r * WL + w] = ids[r] >= 0 ? i8_pack_dword(vectors, ids[r], w, d) : 0u;
+            }
+            return;
+        }
+        int r = r0, w = w0;
+#pragma unroll
+        for (int j = 0; j < NP; j++) {
+            if (r < KM_IT) tl[r * WL + w] = pre[j];
+            r += dr;
+            w += dw;
+            if (w >= W) { w -= W; r++; }
+        }
+    };
+
+    const int ntile = (it.count + KM_IT - 1) / KM_IT;   /* >= 1 */
+    stage_load(0);          /* km_begin's barrier is behind the ids of tiles 0 and 1 */
+    stage_store(0);
+    __syncthreads();
+    const uint32_t* arow = cl + (cb * XQT + col) * WL;
+    const uint32_t* brow = tl + (mb * RI_T + col) * WL;
+    for (int t = 0; t < ntile; t++) {
+        if (t + 1 < ntile) stage_load(t + 1);   /* in flight while this tile computes */
+        v16i acc;
+        int bb;
+        i8_tile_dots<DM>(arow, brow, W, h, acc, bb);
+        /* acc[r] is center cb*32 + 8*(r/4) + 4*h + r%4 against member mb*32 + col */
+        float* row = ctx.dmat + (mb * RI_T + col) * KM_DS;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int k = cb * XQT + 8 * (r >> 2) + 4 * h + (r & 3);
+            row[k] = (DM == DM_L2) ? (float)(caa[k] - 2 * acc[r] + bb) : (float)(16129 - acc[r]);
+        }
+        __syncthreads();
+        km_choose(ctx, A, it, wave * RPW, RPW, t * KM_IT);
+        __syncthreads();
+        if (A.update && L.ss >= d)
+            km_tile_sums(sums, L.ss, ctx, t * KM_IT, min((int)KM_IT, it.count - t * KM_IT),
+                         t + 1 == ntile, d, part, [&](int mi, int c) {
+                             const uint32_t v = tl[(mi - t * KM_IT) * WL + (c >> 2)];
+                             return (int)(int8_t)(v >> (8 * (c & 3)));
+                         });
+        if (t + 1 < ntile) stage_store(t + 1);
+        /* tile t's ids are done with: tile t + 2's take their place */
+        if (tid < KM_IT) mids[(t & 1) * KM_IT + tid] = idn;
+        idn = tile_id(t + 3);
+        __syncthreads();
+    }
+    if (A.update && L.ss < d)       /* the sums do not fit beside the tile */
+        km_item_sums(sums, L.ss, ctx, it.count, d, part,
+                     [&](int mi, int c) { return (int)vectors[(size_t)mem[mi] * d + c]; });
+    km_end(ctx, A, it);
+}
+
+/* ------------------------------------------------------------------ *
  * launchers
  * ------------------------------------------------------------------ */
 
@@ -2107,6 +2644,60 @@ int launch_pool_join(int vt, int dm, const void* vectors, int32_t dim, const int
                            nullptr, (const int8_t*)vectors, dim, nodes, pool_ids, pool_dists,
                            npool, new_ids, nnew, kout, out_ids, out_dists);
     }
+    return (int)hipGetLastError();
+}
+
+int kmeans_assign_tile(int vt) { return vt == VT_FLOAT ? (int)FRT : (int)KM_IT; }
+
+int kmeans_assign_item_tiles(int vt, int64_t ntiles)
+{
+    const int64_t cap = KM_ITEM_MAX / kmeans_assign_tile(vt);
+    const int64_t want = (ntiles + KM_ITEMS_TARGET - 1) / KM_ITEMS_TARGET;
+    return (int)(want < 1 ? 1 : want > cap ? cap : want);
+}
+
+int launch_kmeans_assign(int vt, int dm, const void* vectors, int32_t dim, const KmArgs& A)
+{
+    /* the kernels index nothing outside these bounds */
+    if (A.nseg < 1 || A.nitems < 0 || A.kmax < 1 || A.kmax > KM_MAX_K || dim < 1 ||
+        dim > MAX_DIM || (vt != VT_FLOAT && vt != VT_INT8) ||
+        (vt == VT_INT8 && dim > 4 * I_MAX_W) || (A.update && !(A.out_sums && A.partials)) ||
+        (A.lambdas != nullptr) != (A.prev_counts != nullptr))
+        return (int)hipErrorInvalidValue;
+    const size_t cells = (size_t)A.nseg * A.kmax;
+    const size_t iblocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(kmeans_init_kernel, dim3(iblocks < 65536 ? (unsigned)iblocks : 65536u),
+                       dim3(256), 0, nullptr, A);
+    const int nqt = A.kmax > XQT ? 2 : 1;
+    if (A.nitems > 0 && vt == VT_FLOAT) {
+        const bool res = km_f32_resident(dim, nqt, A.kmax, A.update);
+        const KmLds L = km_f32_lds(dim, nqt, A.kmax, A.update, res);
+        if (L.total > KM_LDS_MAX || (A.update && L.ss < 4)) return (int)hipErrorInvalidValue;
+        auto pick = [&](auto k11, auto k12, auto k01, auto k02) {
+            return res ? (nqt == 1 ? k11 : k12) : (nqt == 1 ? k01 : k02);
+        };
+        auto kernel = dm == DM_L2
+            ? pick(kmeans_f32_kernel<DM_L2, true, 1>, kmeans_f32_kernel<DM_L2, true, 2>,
+                   kmeans_f32_kernel<DM_L2, false, 1>, kmeans_f32_kernel<DM_L2, false, 2>)
+            : pick(kmeans_f32_kernel<DM_COSINE, true, 1>, kmeans_f32_kernel<DM_COSINE, true, 2>,
+                   kmeans_f32_kernel<DM_COSINE, false, 1>,
+                   kmeans_f32_kernel<DM_COSINE, false, 2>);
+        hipLaunchKernelGGL(kernel, dim3(A.nitems), dim3(XTHREADS), L.total, nullptr,
+                           (const float*)vectors, dim, A);
+    } else if (A.nitems > 0) {
+        const KmLds L = km_i8_lds(dim, nqt, A.kmax, A.update);
+        if (L.total > KM_LDS_MAX || (A.update && L.ss < 4)) return (int)hipErrorInvalidValue;
+        auto kernel = dm == DM_L2
+            ? (nqt == 1 ? kmeans_i8_kernel<DM_L2, 1> : kmeans_i8_kernel<DM_L2, 2>)
+            : (nqt == 1 ? kmeans_i8_kernel<DM_COSINE, 1> : kmeans_i8_kernel<DM_COSINE, 2>);
+        hipLaunchKernelGGL(kernel, dim3(A.nitems), dim3(128 * nqt), L.total, nullptr,
+                           (const int8_t*)vectors, dim, A);
+    }
+    const dim3 fgrid(A.nseg, A.update ? ((unsigned)A.kmax * dim + 255) / 256 : 1);
+    if (vt == VT_INT8)
+        hipLaunchKernelGGL(kmeans_finish_kernel<true>, fgrid, dim3(256), 0, nullptr, A, dim);
+    else
+        hipLaunchKernelGGL(kmeans_finish_kernel<false>, fgrid, dim3(256), 0, nullptr, A, dim);
     return (int)hipGetLastError();
 }
 

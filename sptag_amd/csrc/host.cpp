@@ -1244,6 +1244,174 @@ int sptag_amd_pool_join(SptagAmdIndex* ix, const int32_t* nodes, int32_t nrows,
     return SPTAG_AMD_OK;
 }
 
+/* What both k-means-assign entries can check from the host: the pointers, kmax
+ * and every ncenters, and that every segment is a range of the member list
+ * and no two ranges overlap. */
+static bool kmeans_args_ok(const void* members, int64_t nmembers, const int32_t* starts,
+                           const int32_t* sizes, const int32_t* ncenters, int32_t nseg,
+                           const void* centers, int32_t kmax, const void* prev_counts,
+                           const void* lambdas, int32_t update, const void* labels,
+                           const void* counts, const void* cidx, const void* cdist,
+                           const void* sums)
+{
+    if (!members || !centers || !ncenters || !labels || !counts || !cidx || !cdist ||
+        kmax < 1 || kmax > KMEANS_MAX_K || (update != 0 && update != 1) ||
+        (update == 1 && !sums) || (prev_counts != nullptr) != (lambdas != nullptr) ||
+        !group_ranges_ok(nmembers, starts, sizes, nseg, 1))
+        return false;
+    for (int32_t s = 0; s < nseg; s++)
+        if (ncenters[s] < 1 || ncenters[s] > kmax) return false;
+    return true;
+}
+
+/* k-means assign into device buffers, arguments checked; `device` is current.
+ * Returns once the output is complete. */
+static int kmeans_assign_core(const void* d_vectors, int vt, int dm, int32_t dim,
+                              const int32_t* starts, const int32_t* sizes,
+                              const int32_t* ncenters, int32_t nseg, KmArgs A)
+{
+    /* the work list: a segment's items are consecutive runs of whole tiles */
+    const int tile = kmeans_assign_tile(vt);
+    int64_t ntiles = 0;
+    for (int32_t s = 0; s < nseg; s++) ntiles += ((int64_t)sizes[s] + tile - 1) / tile;
+    const int32_t run = tile * kmeans_assign_item_tiles(vt, ntiles);
+    std::vector<KmItem> items;
+    std::vector<KmSeg> segs((size_t)nseg);
+    for (int32_t s = 0; s < nseg; s++) {
+        segs[s].ncenters = ncenters[s];
+        segs[s].item0 = (int32_t)items.size();
+        for (int32_t p = 0; p < sizes[s]; p += run)
+            items.push_back({s, starts[s] + p, std::min(run, sizes[s] - p), p});
+        segs[s].nitems = (int32_t)items.size() - segs[s].item0;
+    }
+    if (items.size() > (size_t)INT32_MAX) return SPTAG_AMD_ERR_PARAM;
+    DevBuf d_items, d_segs, d_keys, d_part;
+    int rc = dev_upload(d_segs, segs.data(), segs.size() * sizeof(KmSeg));
+    if (rc == SPTAG_AMD_OK && !items.empty())
+        rc = dev_upload(d_items, items.data(), items.size() * sizeof(KmItem));
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(d_keys.alloc((size_t)nseg * A.kmax * 8), SPTAG_AMD_ERR_OOM);
+    if (A.update)
+        HIP_OR_FAIL(d_part.alloc(std::max<size_t>(items.size(), 1) * A.kmax * dim * 4),
+                    SPTAG_AMD_ERR_OOM);
+    A.items = d_items.as<KmItem>();
+    A.segs = d_segs.as<KmSeg>();
+    A.nseg = nseg;
+    A.nitems = (int32_t)items.size();
+    A.keys = d_keys.as<unsigned long long>();
+    A.partials = d_part.as();
+    int err = launch_kmeans_assign(vt, dm, d_vectors, dim, A);
+    if (err != 0) {
+        fprintf(stderr, "sptag_amd: kmeans assign launch failed %d\n", err);
+        return SPTAG_AMD_ERR_INTERNAL;
+    }
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
+int sptag_amd_kmeans_assign_device(int device, const void* d_vectors, int valuetype,
+                                   int distmethod, int32_t n, int32_t dim,
+                                   const int32_t* d_members, int32_t nmembers,
+                                   const int32_t* seg_starts, const int32_t* seg_sizes,
+                                   const int32_t* ncenters, int32_t nseg,
+                                   const void* d_centers, int32_t kmax,
+                                   const int32_t* d_prev_counts, const float* d_lambdas,
+                                   int32_t update, int32_t* d_out_labels, float* d_out_dists,
+                                   int32_t* d_out_counts, int32_t* d_out_cluster_idx,
+                                   float* d_out_cluster_dist, float* d_out_sums)
+{
+    if (!d_vectors || n < 1 || dim < 1 || dim > MAX_DIM ||
+        (valuetype != VT_FLOAT && valuetype != VT_INT8) ||
+        (distmethod != DM_L2 && distmethod != DM_COSINE) ||
+        (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) ||
+        !kmeans_args_ok(d_members, nmembers, seg_starts, seg_sizes, ncenters, nseg, d_centers,
+                        kmax, d_prev_counts, d_lambdas, update, d_out_labels, d_out_counts,
+                        d_out_cluster_idx, d_out_cluster_dist, d_out_sums))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    KmArgs A = {};
+    A.members = d_members;
+    A.centers = d_centers;
+    A.prev_counts = d_prev_counts;
+    A.lambdas = d_lambdas;
+    A.kmax = kmax;
+    A.update = update;
+    A.out_labels = d_out_labels;
+    A.out_dists = d_out_dists;
+    A.out_counts = d_out_counts;
+    A.out_cluster_idx = d_out_cluster_idx;
+    A.out_cluster_dist = d_out_cluster_dist;
+    A.out_sums = update ? d_out_sums : nullptr;
+    return kmeans_assign_core(d_vectors, valuetype, distmethod, dim, seg_starts, seg_sizes,
+                              ncenters, nseg, A);
+}
+
+int sptag_amd_kmeans_assign(SptagAmdIndex* ix, const int32_t* members, int32_t nmembers,
+                            const int32_t* seg_starts, const int32_t* seg_sizes,
+                            const int32_t* ncenters, int32_t nseg, const void* centers,
+                            int32_t kmax, const int32_t* prev_counts, const float* lambdas,
+                            int32_t update, int32_t* out_labels, float* out_dists,
+                            int32_t* out_counts, int32_t* out_cluster_idx,
+                            float* out_cluster_dist, float* out_sums)
+{
+    if (!ix || !kmeans_args_ok(members, nmembers, seg_starts, seg_sizes, ncenters, nseg,
+                               centers, kmax, prev_counts, lambdas, update, out_labels,
+                               out_counts, out_cluster_idx, out_cluster_dist, out_sums))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available() || !ix->d_vectors) return SPTAG_AMD_ERR_NOGPU;
+    std::lock_guard<std::mutex> g(ix->lock);
+    for (int32_t i = 0; i < nmembers; i++)
+        if (members[i] < 0 || members[i] >= ix->n) return SPTAG_AMD_ERR_PARAM;
+    HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
+
+    /* the outputs go up as they are and come back whole, so what the kernels
+     * leave alone (positions in no segment, centers past ncenters) stays */
+    const size_t nm = (size_t)std::max(nmembers, 1), cells = (size_t)nseg * kmax;
+    DevBuf d_mem, d_cen, d_pc, d_lam, d_lab, d_dist, d_cnt, d_ci, d_cd, d_sums;
+    int rc;
+    if ((rc = dev_upload(d_mem, nmembers ? members : seg_starts, nm * 4)) != SPTAG_AMD_OK ||
+        (rc = dev_upload(d_cen, centers, cells * ix->dim * ix->esz())) != SPTAG_AMD_OK ||
+        (rc = dev_upload(d_lab, nmembers ? out_labels : seg_starts, nm * 4)) != SPTAG_AMD_OK ||
+        (rc = dev_upload(d_cnt, out_counts, cells * 4)) != SPTAG_AMD_OK ||
+        (rc = dev_upload(d_ci, out_cluster_idx, cells * 4)) != SPTAG_AMD_OK ||
+        (rc = dev_upload(d_cd, out_cluster_dist, cells * 4)) != SPTAG_AMD_OK)
+        return rc;
+    if (out_dists && nmembers && (rc = dev_upload(d_dist, out_dists, nm * 4)) != SPTAG_AMD_OK)
+        return rc;
+    if (lambdas && ((rc = dev_upload(d_pc, prev_counts, cells * 4)) != SPTAG_AMD_OK ||
+                    (rc = dev_upload(d_lam, lambdas, (size_t)nseg * 4)) != SPTAG_AMD_OK))
+        return rc;
+    if (update && (rc = dev_upload(d_sums, out_sums, cells * ix->dim * 4)) != SPTAG_AMD_OK)
+        return rc;
+    KmArgs A = {};
+    A.members = d_mem.as<int32_t>();
+    A.centers = d_cen.as();
+    A.prev_counts = d_pc.as<int32_t>();
+    A.lambdas = d_lam.as<float>();
+    A.kmax = kmax;
+    A.update = update;
+    A.out_labels = d_lab.as<int32_t>();
+    A.out_dists = d_dist.as<float>();
+    A.out_counts = d_cnt.as<int32_t>();
+    A.out_cluster_idx = d_ci.as<int32_t>();
+    A.out_cluster_dist = d_cd.as<float>();
+    A.out_sums = d_sums.as<float>();
+    rc = kmeans_assign_core(ix->d_vectors.as(), ix->vt, ix->dm, ix->dim, seg_starts, seg_sizes,
+                            ncenters, nseg, A);
+    if (rc != SPTAG_AMD_OK) return rc;
+    auto down = [](void* dst, const DevBuf& b, size_t bytes) {
+        return hipMemcpy(dst, b.as(), bytes, hipMemcpyDeviceToHost);
+    };
+    if (nmembers) HIP_OR_FAIL(down(out_labels, d_lab, nm * 4), SPTAG_AMD_ERR_NOGPU);
+    if (nmembers && out_dists) HIP_OR_FAIL(down(out_dists, d_dist, nm * 4), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(down(out_counts, d_cnt, cells * 4), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(down(out_cluster_idx, d_ci, cells * 4), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(down(out_cluster_dist, d_cd, cells * 4), SPTAG_AMD_ERR_NOGPU);
+    if (update) HIP_OR_FAIL(down(out_sums, d_sums, cells * ix->dim * 4), SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
 /* Host-side distance restatements for the add path's edge arithmetic
  * (RebuildNeighbors / InsertNeighbors recompute pair distances on the
  * host, as the reference does on CPU): same rounding contracts as the
