@@ -340,6 +340,75 @@ int sptag_amd_kmeans_assign_device(int device, const void* d_vectors, int valuet
                                    int32_t* d_out_counts, int32_t* d_out_cluster_idx,
                                    float* d_out_cluster_dist, float* d_out_sums);
 
+/* TP-tree partition: the reference's hyperplane splits (PartitionByTptreeCore,
+ * NeighborhoodGraph.h:152-299) of a member list (vector ids) into leaves, the
+ * step of the index builder that makes the leaves of the kNN candidates. The
+ * list is split level by level, the root being level 0; a segment is
+ * members[first .. first + c). A segment with c <= leaf_size is a leaf (the
+ * reference tests last - first <= leaf, one member more; this is the
+ * builder's own test). A longer one splits as follows, where a coordinate
+ * enters as (float)v[k], every operation is f32 and rounded once, none is
+ * fused, and sums run from 0 in the stated order:
+ *   1. s = min(samples, c); the sample is the first s members in list order,
+ *      v_0 .. v_{s-1}.
+ *   2. Mean[k] = (v_0[k] + v_1[k] + ..) / (float)s; Var[k] = the sum over i in
+ *      order of (v_i[k] - Mean[k])^2.
+ *   3. T = min(topdims, dim); idx_0 .. idx_{T-1} are the dimensions of largest
+ *      Var, ties to the lower dimension, a NaN below every number.
+ *   4. The best rule starts as weights (1, 0, .., 0), bestvar = Var[idx_0],
+ *      bestmean = Mean[idx_0].
+ *   5. For trial t = 0 .. trials - 1 in order: w_j = (float)draw(t, j) /
+ *      5000.0f - 1.0f; norm = sqrt(w_0*w_0 + w_1*w_1 + ..) in order; the trial
+ *      is skipped if norm == 0, else w_j = w_j / norm. Val_i = w_0*v_i[idx_0]
+ *      + w_1*v_i[idx_1] + .., in order of j; mean = (Val_0 + Val_1 + ..) /
+ *      (float)s; var = the sum over i of (Val_i - mean)^2. The trial replaces
+ *      the best rule iff var > bestvar: the earliest of equals wins, and the
+ *      axis rule stays unless strictly beaten.
+ *      draw(t, j), in uint64 wrapping arithmetic: key = (((((uint64)level <<
+ *      31) | first) << 8 | t) << 3) | j; z = seed + 0x9E3779B97F4A7C15 * (1 +
+ *      key); z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ *      0x94D049BB133111EB; z ^= z >> 31; draw = (z >> 32) % 10000. (The
+ *      reference draws from rand() after srand(clock()).)
+ *   6. Each of the c members goes left iff bw_0*v[idx_0] + .. < bestmean, the
+ *      sum as in 5. The split is a STABLE partition: lefts in list order, then
+ *      rights in list order (the reference swaps from both ends, and is not).
+ *      If one side is empty the segment is cut at c / 2 (floor) with the list
+ *      order kept, the reference's rule for equal points.
+ * out_members is a permutation of members; out_leaf_starts / out_leaf_counts
+ * are in ascending start order and tile [0, nmembers) with no gap and no empty
+ * leaf; *out_nleaves is their number. If max_leaves is too small the call
+ * returns SPTAG_AMD_ERR_PARAM with the needed number in *out_nleaves and every
+ * other output untouched. Equal calls give equal bytes. nmembers >= 1,
+ * leaf_size >= 1, 1 <= samples <= 2048, 1 <= topdims <= 8, 0 <= trials <= 256
+ * (trials 0 with topdims 1: a kd-style split of the widest axis at its mean).
+ * The handle form takes host arrays and uses the handle's vectors and value
+ * type; the metric, the delete set, the tree and the graph are not consulted
+ * (BKT and KDT handles alike). Computed by the TP-tree kernels of exact.hip: a
+ * workgroup settles a segment's rule from the sample, the sides are ranked by
+ * ballots and a scan of per-item counts, and the host reads only a left count
+ * per segment and level. Returns SPTAG_AMD_ERR_PARAM, with the outputs
+ * untouched, for a null pointer, a value outside the limits, max_leaves < 0
+ * and a member outside [0, n). */
+int sptag_amd_tpt_partition(SptagAmdIndex* idx, const int32_t* members, int32_t nmembers,
+                            int32_t leaf_size, int32_t samples, int32_t topdims, int32_t trials,
+                            uint64_t seed, int32_t* out_members, int32_t* out_leaf_starts,
+                            int32_t* out_leaf_counts, int32_t max_leaves, int32_t* out_nleaves);
+/* The same without a handle: d_vectors ([n][dim] of valuetype, f32 or int8),
+ * d_members and d_out_members (which may be d_members) are HIP device buffers
+ * on `device`; the leaf table and out_nleaves are host memory. There is no
+ * metric: the rule reads coordinates only. It checks what the host can see
+ * (the pointers, the limits, value type, 1 <= dim <= 4096, the int8 dim guard
+ * of the create calls) and returns SPTAG_AMD_ERR_PARAM for those. That every
+ * member is inside [0, n) is the CALLER'S to guarantee: an id outside makes
+ * the kernels read outside d_vectors. Runs on the default stream and returns
+ * after a device synchronise. */
+int sptag_amd_tpt_partition_device(int device, const void* d_vectors, int valuetype, int32_t n,
+                                   int32_t dim, const int32_t* d_members, int32_t nmembers,
+                                   int32_t leaf_size, int32_t samples, int32_t topdims,
+                                   int32_t trials, uint64_t seed, int32_t* d_out_members,
+                                   int32_t* out_leaf_starts, int32_t* out_leaf_counts,
+                                   int32_t max_leaves, int32_t* out_nleaves);
+
 /* Iterative (streaming) search — mirrors the reference's ResultIterator /
  * SearchIndexIterativeNext protocol (inc/Core/VectorIndex.h:43-49,
  * src/Core/ResultIterator.cpp) over a BATCH of nq per-query iterators whose

@@ -17,6 +17,7 @@ import numpy as np
 
 __all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "group_knn_device",
            "rng_prune_device", "pool_join_device", "kmeans_assign_device",
+           "tpt_partition_device",
            "MetadataSet", "load_library", "gpu_available", "SptagAmdError"]
 
 _LIB = None
@@ -123,6 +124,15 @@ def load_library():
         [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
          ctypes.c_int32, ctypes.c_int32] +
         lib.sptag_amd_kmeans_assign.argtypes[1:])
+    lib.sptag_amd_tpt_partition.restype = ctypes.c_int
+    lib.sptag_amd_tpt_partition.argtypes = (
+        [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 5 +
+        [ctypes.c_uint64] + [ctypes.c_void_p] * 3 +
+        [ctypes.c_int32, ctypes.c_void_p])
+    lib.sptag_amd_tpt_partition_device.restype = ctypes.c_int
+    lib.sptag_amd_tpt_partition_device.argtypes = (
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
+         ctypes.c_int32] + lib.sptag_amd_tpt_partition.argtypes[1:])
     lib.sptag_amd_save_index.restype = ctypes.c_int
     lib.sptag_amd_save_index.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     for f in ["num_vectors", "dim", "valuetype", "distmethod", "degree",
@@ -535,6 +545,30 @@ class AnnIndex:
             raise SptagAmdError(rc, "kmeans_assign")
         return labels, dists, counts, cidx, cdist, sums
 
+    def TptPartition(self, members, leaf_size, samples=1000, topdims=5,
+                     trials=100, seed=0):
+        """TP-tree partition of a member list (vector ids) by the reference's
+        hyperplane rule (include/sptag_amd.h): a segment longer than leaf_size
+        splits at the mean of the projection of largest variance among
+        `trials` random weightings of the `topdims` widest dimensions of its
+        first `samples` members, stably. Returns (members int32 [nmembers]
+        permuted, starts int32 [nleaves], counts int32 [nleaves]): leaf i is
+        members[starts[i] : starts[i] + counts[i]], in ascending start order."""
+        members = np.ascontiguousarray(members, dtype=np.int32)
+        if members.ndim != 1:
+            raise ValueError("members [nmembers] expected")
+        out = np.empty_like(members)
+
+        def call(starts, counts, nleaves):
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+            return self._lib.sptag_amd_tpt_partition(
+                self._h, p(members), members.size, leaf_size, samples,
+                topdims, trials, seed, p(out), p(starts), p(counts),
+                starts.size, ctypes.byref(nleaves))
+        starts, counts = _tpt_leaf_table(call, members.size, leaf_size,
+                                         "tpt_partition")
+        return out, starts, counts
+
     def Add(self, vectors, normalized=False):
         """Online add (reference AddIndex semantics below the tree-rebuild
         threshold); runs GPU refine searches per added vector."""
@@ -684,6 +718,44 @@ def kmeans_assign_device(d_vectors_ptr, valuetype, distmethod, n, dim,
         vp(d_cluster_dist_ptr), vp(d_sums_ptr))
     if rc != 0:
         raise SptagAmdError(rc, "kmeans_assign_device")
+
+
+def _tpt_leaf_table(call, nmembers, leaf_size, what):
+    """Runs call(starts, counts, nleaves) with a modest leaf table and once
+    more with the size the library asked for; returns (starts, counts)."""
+    nleaves = ctypes.c_int32(-1)
+    cap = min(max(nmembers, 1), 64 + 4 * (nmembers // max(leaf_size, 1)))
+    for _ in range(2):
+        starts = np.empty(cap, dtype=np.int32)
+        counts = np.empty(cap, dtype=np.int32)
+        rc = call(starts, counts, nleaves)
+        if rc == 0:
+            return starts[:nleaves.value].copy(), counts[:nleaves.value].copy()
+        if nleaves.value <= cap:
+            break
+        cap = nleaves.value
+    raise SptagAmdError(rc, what)
+
+
+def tpt_partition_device(d_vectors_ptr, valuetype, n, dim, d_members_ptr,
+                         nmembers, leaf_size, d_out_members_ptr, samples=1000,
+                         topdims=5, trials=100, seed=0, device=0):
+    """AnnIndex.TptPartition without a handle, on HIP device addresses (e.g.
+    torch tensors' .data_ptr()): vectors [n, dim] of `valuetype`, int32
+    members and out_members [nmembers]; the output may be the input. Returns
+    the leaf table (starts, counts) as int32 numpy arrays. The caller
+    guarantees that every member is inside [0, n)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None
+    lib = load_library()
+
+    def call(starts, counts, nleaves):
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        return lib.sptag_amd_tpt_partition_device(
+            device, vp(d_vectors_ptr), valuetype, n, dim, vp(d_members_ptr),
+            nmembers, leaf_size, samples, topdims, trials, seed,
+            vp(d_out_members_ptr), p(starts), p(counts), starts.size,
+            ctypes.byref(nleaves))
+    return _tpt_leaf_table(call, nmembers, leaf_size, "tpt_partition_device")
 
 
 def merge_topk(vids, dists, vid_base, k, device=0):

@@ -12,7 +12,10 @@ Mirrors the reference build SEMANTICS (citations to /root/reference/AnnService):
     of this file is judged on bytes against its parent.
   - KNN graph: TP-tree partitions, exact KNN inside each leaf, candidates
     merged over trees (NeighborhoodGraph.h:301-360); the leaf step is torch
-    by default and the grouped-kNN HIP kernels with leaf_knn="hip";
+    by default and the grouped-kNN HIP kernels with leaf_knn="hip"; the
+    partition is a random-direction median split in torch by default and
+    the reference's rule (PartitionByTptreeCore, NeighborhoodGraph.h:152-299)
+    on the TP-tree-partition HIP kernels with tpt="hip";
   - RNG prune: candidates ascending by distance, accept c iff for every
     already-accepted b: RNGFactor*dist(b,c) >= dist(q,c), up to degree, pad
     -1 (RelativeNeighborhoodGraph.h:18-35 RebuildNeighbors).
@@ -549,6 +552,39 @@ def _tpt_leaves(xf, leaf, gen):
     return perm, _seg_starts(counts), counts
 
 
+def _tpt_leaves_hip(xf, leaf, gen):
+    """_tpt_leaves by the TP-tree-partition HIP kernels
+    (sptag_amd.tpt_partition_device): the reference's rule (sample mean and
+    variance, the 5 widest dimensions, 100 random weightings, a split at the
+    mean of the best projection) in place of a dense random direction split
+    at the median. The same return shape; the leaves are ragged, down to one
+    member, and none is empty. The seed is drawn from the generator."""
+    if xf.device.type != "cuda":
+        raise RuntimeError('tpt="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
+    from . import tpt_partition_device, VT_FLOAT
+    n, d = xf.shape
+    dev = xf.device
+    xf = xf.contiguous()
+    seed = int(torch.randint(0, 2 ** 62, (1,), generator=gen, device=dev).item())
+    members = torch.arange(n, device=dev, dtype=torch.int32)
+    torch.cuda.synchronize(dev)     # the library runs on the default stream
+    starts, counts = tpt_partition_device(
+        xf.data_ptr(), VT_FLOAT, n, d, members.data_ptr(), n, leaf,
+        members.data_ptr(), seed=seed, device=dev.index or 0)
+    return (members.long(), torch.as_tensor(starts, device=dev).long(),
+            torch.as_tensor(counts, device=dev).long())
+
+
+def _tpt_fn(tpt):
+    """the TP-tree partition by name: f(xf, leaf, gen)"""
+    if tpt == "torch":
+        return _tpt_leaves
+    if tpt == "hip":
+        return _tpt_leaves_hip
+    raise ValueError(f'tpt must be "torch" or "hip", got {tpt!r}')
+
+
 def _leaf_knn(xf, perm, starts, counts, kper, chunk_rows=1_000_000):
     """Exact KNN inside each leaf. Returns (ids int32 [n,kper], dists f32) in
     original vector-id space (L2 on the f32 view; candidate generation only —
@@ -856,7 +892,7 @@ def _prune_fn(prune):
 def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
                     rng_factor=1.0, seed=2016, device=None, point_chunk=None,
                     verbose=False, leaf_knn="torch", prune="torch",
-                    join="torch"):
+                    join="torch", tpt="torch"):
     """Returns (graph, cand_ids, cand_dst), tensors on the device: graph
     int32 [n, degree] (RNG-pruned, ascending, -1 padded) and the [n, cand]
     candidate pools it was pruned from, which the refine steps grow.
@@ -865,7 +901,11 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
     prune: "torch" (_rng_prune) or "hip" (the RNG-prune kernels; GPU only)
     for the RebuildNeighbors step.
     join: "torch" (_exact_l2 + _merge_candidates) or "hip" (the pool-join
-    kernels; GPU only) for every step that grows a candidate pool."""
+    kernels; GPU only) for every step that grows a candidate pool.
+    tpt: "torch" (_tpt_leaves: a dense random direction a level, split at the
+    median) or "hip" (the TP-tree-partition kernels, the reference's rule; GPU
+    only; ragged leaves) for the partitions that make the leaves."""
+    tpt_fn = _tpt_fn(tpt)
     if leaf_knn not in _LEAF_KNN:
         raise ValueError(f'leaf_knn must be "torch" or "hip", got {leaf_knn!r}')
     prune_fn = _prune_fn(prune)
@@ -877,13 +917,16 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
     if join == "hip" and xf.device.type != "cuda":
         raise RuntimeError('join="hip" needs the vectors on a GPU, got '
                            f"device {xf.device}")
+    if tpt == "hip" and xf.device.type != "cuda":
+        raise RuntimeError('tpt="hip" needs the vectors on a GPU, got '
+                           f"device {xf.device}")
     n = xf.shape[0]
     self_ids = torch.arange(n, device=device, dtype=torch.int32)
 
     kper = min(max(33, cand // max(ntrees, 1)), 64)
     ids = dst = None
     for t in range(ntrees):
-        perm, starts, counts = _tpt_leaves(xf, tpt_leaf, gen)
+        perm, starts, counts = tpt_fn(xf, tpt_leaf, gen)
         tids, tdst = _LEAF_KNN[leaf_knn](xf, perm, starts, counts, kper)
         if ids is None:
             ids, dst = join_fn(xf, tids, tdst, tids[:, :0], tdst[:, :0],
@@ -1106,16 +1149,18 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
                        srefine_k=512, srefine_mc=8192, fill_pruned=False,
                        seed=2016, device=None, normalized=False,
                        verbose=False, leaf_knn="torch", prune="torch",
-                       join="torch", kmeans="torch"):
+                       join="torch", kmeans="torch", tpt="torch"):
     """Full build: returns dict(vectors, tree_start, tree_nodes, graph) ready
     for AnnIndex.FromArrays (vectors already cosine-normalized when needed,
     as the reference stores them on disk). prune: "torch" or "hip" (GPU
     only), the RebuildNeighbors step of every graph stage; join: likewise,
     the step that grows the candidate pools; kmeans: likewise, the cluster
-    splits of the BKT tree."""
+    splits of the BKT tree; tpt: likewise, the TP-tree partitions that make
+    the graph's leaves."""
     _prune_fn(prune)
     _join_fn(join)
     _check_kmeans(kmeans)
+    _tpt_fn(tpt)
     if not normalized:
         vectors = normalize_base(vectors, distmethod)
     if algo == "KDT":
@@ -1130,7 +1175,7 @@ def build_index_arrays(vectors, distmethod, *, algo="BKT", degree=32, ntrees=4,
     graph, cids, cdst = build_rng_graph(
         vectors, degree=degree, ntrees=ntrees, tpt_leaf=tpt_leaf, cand=cand,
         seed=seed, device=device, verbose=verbose, leaf_knn=leaf_knn,
-        prune=prune, join=join)
+        prune=prune, join=join, tpt=tpt)
     if refine_rounds > 0:
         graph, cids, cdst = refine_graph(
             vectors, graph, cids, cdst, degree=degree, cand=cand,

@@ -287,6 +287,40 @@ int kmeans_assign_item_tiles(int valuetype, int64_t ntiles);
 int launch_kmeans_assign(int valuetype, int distmethod, const void* vectors, int32_t dim,
                          const KmArgs& args);
 
+/* TP-tree partition (exact.hip): one level of hyperplane splits over the open
+ * segments of one member list. Segment s is cur[first : first + count] at tree
+ * level `level`; its items (at most TPT_ITEM members each, consecutive, in
+ * list order) are items[item0 .. item0 + nitems). launch_tpt_level runs four
+ * kernels: the rule (one workgroup a segment, by the rule of
+ * include/sptag_amd.h), the sides (one workgroup an item: a left bit and the
+ * lefts before it inside the item, packed into codes; a left count per item),
+ * the scan (item bases and seg_left, a segment's lefts) and the scatter: a
+ * member goes to its stable place in `next`, or in `fin` when its child is
+ * at most leaf_size long. A seg_left of 0 or `count` is the rank cut at
+ * count / 2, which the host applies to its tables as the scatter does. All
+ * pointers are device memory; every member is inside the vectors; cur, next
+ * and fin are three different lists. */
+enum { TPT_ITEM = 256, TPT_MAX_SAMPLES = 2048, TPT_MAX_DIMS = 8, TPT_MAX_TRIALS = 256 };
+struct TptSeg { int32_t first, count, level, item0, nitems; };
+struct TptItem { int32_t seg, start, count, pos0; };
+struct TptRule { int32_t idx[TPT_MAX_DIMS]; float w[TPT_MAX_DIMS]; float mean; };
+struct TptArgs {
+    const int32_t* cur;
+    int32_t* next;
+    int32_t* fin;
+    const TptSeg* segs;
+    const TptItem* items;
+    int32_t nseg, nitems;
+    int32_t leaf_size, samples, topdims, trials;
+    uint64_t seed;
+    TptRule* rules;         /* [nseg] scratch */
+    int32_t* codes;         /* [list length] scratch, indexed as cur */
+    int32_t* item_left;     /* [nitems] scratch */
+    int32_t* item_base;     /* [nitems] scratch */
+    int32_t* seg_left;      /* [nseg] out */
+};
+int launch_tpt_level(int valuetype, const void* vectors, int32_t dim, const TptArgs& args);
+
 /* heap probe (tests/test_gpu_heap_ops.py): a script of nops heap operations
  * (ops[i] != 0: insert {nodes[i], dists[i]}; 0: pop) on a heap of capacity
  * `cap` whose entries [0..lsplit] sit in LDS (lsplit 0: none), run once with

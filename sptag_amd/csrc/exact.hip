@@ -2501,6 +2501,317 @@ void kmeans_i8_kernel(const int8_t* __restrict__ vectors, int d, KmArgs A)
 }
 
 /* ------------------------------------------------------------------ *
+ * TP-tree partition: one level of the reference's hyperplane splits
+ * (PartitionByTptreeCore, NeighborhoodGraph.h:152-299) over the open segments
+ * of a member list, by the rule of include/sptag_amd.h. Four kernels a level:
+ *   rule     one workgroup a segment. A thread owns columns (stride
+ *            TP_THREADS) and walks the sample rows in order, TP_AHEAD rows'
+ *            loads in flight ahead of the dependent adds: every step reads
+ *            one row coalesced and the sums have the contract's order. The
+ *            variance pass reads the rows again (L2). Var and Mean go to LDS;
+ *            T rounds of a workgroup arg-max (wave butterfly, then one entry
+ *            a wave in LDS) pick the dimensions. The sample's T columns are
+ *            staged as [s][T] f32 over the same LDS; thread t owns trial t
+ *            and walks the staged sample twice, every lane at one address (a
+ *            broadcast). The winner, or thread 0 for the axis rule, writes
+ *            the segment's TptRule.
+ *   sides    one workgroup an item, one member a thread: T column loads, the
+ *            projection, the side as a bit; ballot and popcount give the
+ *            lefts before a member in its wave, LDS the waves before it.
+ *   scan     one wave a segment: exclusive scan of the items' left counts.
+ *   scatter  one workgroup an item: the stable place of every member, in
+ *            `fin` when its child is a leaf already, else in `next`.
+ * No loop's end depends on data that a kernel computed.
+ * ------------------------------------------------------------------ */
+
+enum {
+    TP_THREADS = 256,
+    TP_WAVES = TP_THREADS / 64,
+    TP_AHEAD = 8,                   /* sample rows in flight in the column walks */
+    TP_SCRATCH = 2 * TP_WAVES * 4,  /* the arg-max's entries, in front of Var and Mean */
+    TP_LDS_MAX = 65536,
+};
+static_assert(TPT_MAX_TRIALS <= TP_THREADS && TPT_ITEM == TP_THREADS &&
+                  TPT_MAX_SAMPLES * TPT_MAX_DIMS * 4 <= TP_LDS_MAX &&
+                  TP_SCRATCH + 8 * MAX_DIM <= TP_LDS_MAX,
+              "a trial a thread, a member a thread, the sample in LDS");
+
+/* The contract's arithmetic: f32, rounded once, never fused. The pragma keeps
+ * the contract flag off the instruction, so no later pass joins it with a
+ * neighbour into an fma; division and square root are the correctly rounded
+ * ones (__fsqrt_rn of this toolchain is the native, approximate one). */
+DEV float tp_add(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+DEV float tp_sub(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+DEV float tp_mul(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+DEV float tp_div(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a / b;
+}
+DEV float tp_sqrt(float a) { return __builtin_sqrtf(a); }
+
+template <class VT>
+DEV float tp_load(const VT* __restrict__ vectors, int32_t m, int32_t dim, int k)
+{
+    return (float)vectors[(size_t)m * dim + k];
+}
+
+/* w_0*x_0 + .. + w_{T-1}*x_{T-1}, summed from 0 in order */
+DEV float tp_dot(const float* x, const float* w, int T)
+{
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < TPT_MAX_DIMS; j++)
+        if (j < T) acc = tp_add(acc, tp_mul(w[j], x[j]));
+    return acc;
+}
+
+/* entry (va, da) ranks before (vb, db): the larger value, a NaN below every
+ * number, then the lower index; an index < 0 is no entry */
+DEV bool tp_rank_before(float va, int da, float vb, int db)
+{
+    if (da < 0) return false;
+    if (db < 0) return true;
+    const bool above = va > vb || (vb != vb && va == va);
+    const bool below = vb > va || (va != va && vb == vb);
+    return above || (!below && da < db);
+}
+
+/* the workgroup's first-ranked entry, in every thread; sv/sd: LDS [TP_WAVES] */
+DEV void tp_block_best(float& v, int& d, float* sv, int* sd)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int od = __shfl_xor(d, o);
+        if (tp_rank_before(ov, od, v, d)) { v = ov; d = od; }
+    }
+    __syncthreads();        /* the entries of the round before are read */
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; sd[threadIdx.x >> 6] = d; }
+    __syncthreads();
+    v = sv[0];
+    d = sd[0];
+    for (int w = 1; w < TP_WAVES; w++)
+        if (tp_rank_before(sv[w], sd[w], v, d)) { v = sv[w]; d = sd[w]; }
+}
+
+/* draw(t, j) of the segment at (level, first): a pure function of its key */
+DEV uint32_t tp_draw(uint64_t seed, uint32_t level, uint32_t first, uint32_t t, uint32_t j)
+{
+    const uint64_t key = ((((((uint64_t)level << 31) | first) << 8) | t) << 3) | j;
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (1 + key);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (uint32_t)(z >> 32) % 10000u;
+}
+
+/* one column's walk over the sample rows: f(acc, x) in row order */
+template <class VT, class F>
+DEV float tp_column_walk(const VT* __restrict__ vectors, int32_t dim, const int32_t* mem, int s,
+                         int k, F f)
+{
+    float acc = 0.f;
+    int i = 0;
+    for (; i + TP_AHEAD <= s; i += TP_AHEAD) {
+        float x[TP_AHEAD];
+#pragma unroll
+        for (int u = 0; u < TP_AHEAD; u++) x[u] = tp_load(vectors, mem[i + u], dim, k);
+#pragma unroll
+        for (int u = 0; u < TP_AHEAD; u++) acc = f(acc, x[u]);
+    }
+    for (; i < s; i++) acc = f(acc, tp_load(vectors, mem[i], dim, k));
+    return acc;
+}
+
+template <class VT>
+__global__ __launch_bounds__(TP_THREADS)
+void tpt_rule_kernel(const VT* __restrict__ vectors, int32_t dim, TptArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
+    const TptSeg sg = A.segs[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int s = min(A.samples, sg.count), T = min(A.topdims, dim);
+    const int32_t* mem = A.cur + sg.first;
+    const float fs = (float)s;
+    float* sv = (float*)xlds;                   /* [TP_WAVES] */
+    int* sd = (int*)(sv + TP_WAVES);            /* [TP_WAVES] */
+    float* var = (float*)(xlds + TP_SCRATCH);   /* [dim] */
+    float* mean = var + dim;                    /* [dim] */
+    float* stage = (float*)xlds;                /* [s][T], once var and mean are read */
+
+    for (int k = tid; k < dim; k += TP_THREADS) {
+        const float sum = tp_column_walk(vectors, dim, mem, s, k,
+                                         [](float a, float x) { return tp_add(a, x); });
+        const float mu = tp_div(sum, fs);
+        var[k] = tp_column_walk(vectors, dim, mem, s, k, [mu](float a, float x) {
+            const float df = tp_sub(x, mu);
+            return tp_add(a, tp_mul(df, df));
+        });
+        mean[k] = mu;
+    }
+    __syncthreads();
+
+    int idx[TPT_MAX_DIMS];
+#pragma unroll
+    for (int r = 0; r < TPT_MAX_DIMS; r++) {
+        idx[r] = 0;
+        if (r < T) {        /* uniform: the barriers inside are met by all */
+            float bv = 0.f;
+            int bd = -1;
+            for (int k = tid; k < dim; k += TP_THREADS) {
+                bool taken = false;
+#pragma unroll
+                for (int q = 0; q < TPT_MAX_DIMS; q++) taken |= q < r && idx[q] == k;
+                const float vk = var[k];
+                if (!taken && tp_rank_before(vk, k, bv, bd)) { bv = vk; bd = k; }
+            }
+            tp_block_best(bv, bd, sv, sd);
+            idx[r] = bd;
+        }
+    }
+    const float axis_var = var[idx[0]], axis_mean = mean[idx[0]];
+    __syncthreads();
+
+    for (int i = tid; i < s; i += TP_THREADS) {
+        const int32_t m = mem[i];
+#pragma unroll
+        for (int j = 0; j < TPT_MAX_DIMS; j++)
+            if (j < T) stage[i * T + j] = tp_load(vectors, m, dim, idx[j]);
+    }
+    __syncthreads();
+
+    float w[TPT_MAX_DIMS], tvar = 0.f, tmean = 0.f;
+    int tt = -1;
+#pragma unroll
+    for (int j = 0; j < TPT_MAX_DIMS; j++) w[j] = 0.f;
+    if (tid < A.trials) {
+        float nn = 0.f;
+#pragma unroll
+        for (int j = 0; j < TPT_MAX_DIMS; j++)
+            if (j < T) {
+                const uint32_t dr = tp_draw(A.seed, (uint32_t)sg.level, (uint32_t)sg.first,
+                                            (uint32_t)tid, (uint32_t)j);
+                w[j] = tp_sub(tp_div((float)dr, 5000.0f), 1.0f);
+                nn = tp_add(nn, tp_mul(w[j], w[j]));
+            }
+        const float norm = tp_sqrt(nn);
+        if (!(norm == 0.f)) {
+#pragma unroll
+            for (int j = 0; j < TPT_MAX_DIMS; j++)
+                if (j < T) w[j] = tp_div(w[j], norm);
+            float sum = 0.f;
+            for (int i = 0; i < s; i++) sum = tp_add(sum, tp_dot(stage + i * T, w, T));
+            const float mu = tp_div(sum, fs);
+            float acc = 0.f;
+            for (int i = 0; i < s; i++) {
+                const float df = tp_sub(tp_dot(stage + i * T, w, T), mu);
+                acc = tp_add(acc, tp_mul(df, df));
+            }
+            if (acc > axis_var) { tvar = acc; tmean = mu; tt = tid; }
+        }
+    }
+    /* the largest variance, the earliest trial among equals: what keeping a
+     * trial iff it is strictly above the best so far ends at */
+    float bv = tvar;
+    int bt = tt;
+    tp_block_best(bv, bt, sv, sd);      /* its first barrier is behind the last read of stage */
+
+    if (bt >= 0 ? tid == bt : tid == 0) {
+        TptRule* R = A.rules + blockIdx.x;
+#pragma unroll
+        for (int j = 0; j < TPT_MAX_DIMS; j++) {
+            R->idx[j] = idx[j];
+            R->w[j] = bt >= 0 ? w[j] : (j == 0 ? 1.f : 0.f);
+        }
+        R->mean = bt >= 0 ? tmean : axis_mean;
+    }
+}
+
+template <class VT>
+__global__ __launch_bounds__(TP_THREADS)
+void tpt_side_kernel(const VT* __restrict__ vectors, int32_t dim, TptArgs A)
+{
+    __shared__ int wl[TP_WAVES];
+    const TptItem it = A.items[blockIdx.x];
+    const TptRule* R = A.rules + it.seg;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = min(A.topdims, dim);
+    bool left = false;
+    if (tid < it.count) {
+        const int32_t m = A.cur[it.start + tid];
+        float x[TPT_MAX_DIMS], w[TPT_MAX_DIMS];
+#pragma unroll
+        for (int j = 0; j < TPT_MAX_DIMS; j++) {
+            x[j] = j < T ? tp_load(vectors, m, dim, R->idx[j]) : 0.f;
+            w[j] = R->w[j];
+        }
+        left = tp_dot(x, w, T) < R->mean;
+    }
+    const uint64_t b = __ballot(left);
+    int before = __popcll(b & ((1ull << lane) - 1));
+    if (lane == 0) wl[wave] = __popcll(b);
+    __syncthreads();
+    int total = 0;
+#pragma unroll
+    for (int v = 0; v < TP_WAVES; v++) {
+        if (v < wave) before += wl[v];
+        total += wl[v];
+    }
+    if (tid < it.count) A.codes[it.start + tid] = (before << 1) | (left ? 1 : 0);
+    if (tid == 0) A.item_left[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(64)
+void tpt_scan_kernel(TptArgs A)
+{
+    const TptSeg sg = A.segs[blockIdx.x];
+    const int lane = threadIdx.x;
+    int carry = 0;
+    for (int base = 0; base < sg.nitems; base += 64) {
+        const int i = base + lane;
+        const int x = i < sg.nitems ? A.item_left[sg.item0 + i] : 0;
+        int inc = x;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(inc, o);
+            if (lane >= o) inc += y;
+        }
+        if (i < sg.nitems) A.item_base[sg.item0 + i] = carry + inc - x;
+        carry += __shfl(inc, 63);
+    }
+    if (lane == 0) A.seg_left[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(TP_THREADS)
+void tpt_scatter_kernel(TptArgs A)
+{
+    const TptItem it = A.items[blockIdx.x];
+    const TptSeg sg = A.segs[it.seg];
+    const int tid = threadIdx.x;
+    if (tid >= it.count) return;
+    const int total = A.seg_left[it.seg], c = sg.count, p = it.pos0 + tid;
+    const int code = A.codes[it.start + tid];
+    const int lb = A.item_base[blockIdx.x] + (code >> 1);      /* lefts before p */
+    const bool cut = total == 0 || total == c;                  /* by rank: order kept */
+    const int nl = cut ? c / 2 : total;
+    const bool left = cut ? p < nl : (code & 1) != 0;
+    const int dest = cut ? p : left ? lb : nl + (p - lb);
+    int32_t* out = (left ? nl : c - nl) <= A.leaf_size ? A.fin : A.next;
+    out[sg.first + dest] = A.cur[it.start + tid];
+}
+
+/* ------------------------------------------------------------------ *
  * launchers
  * ------------------------------------------------------------------ */
 
@@ -2698,6 +3009,34 @@ int launch_kmeans_assign(int vt, int dm, const void* vectors, int32_t dim, const
         hipLaunchKernelGGL(kmeans_finish_kernel<true>, fgrid, dim3(256), 0, nullptr, A, dim);
     else
         hipLaunchKernelGGL(kmeans_finish_kernel<false>, fgrid, dim3(256), 0, nullptr, A, dim);
+    return (int)hipGetLastError();
+}
+
+int launch_tpt_level(int vt, const void* vectors, int32_t dim, const TptArgs& A)
+{
+    /* the kernels index nothing outside these bounds */
+    if (A.nseg < 1 || A.nitems < 1 || A.leaf_size < 1 || A.samples < 1 ||
+        A.samples > TPT_MAX_SAMPLES || A.topdims < 1 || A.topdims > TPT_MAX_DIMS ||
+        A.trials < 0 || A.trials > TPT_MAX_TRIALS || dim < 1 || dim > MAX_DIM ||
+        (vt != VT_FLOAT && vt != VT_INT8) || A.cur == A.next || A.cur == A.fin ||
+        A.next == A.fin)
+        return (int)hipErrorInvalidValue;
+    const size_t T = (size_t)std::min(A.topdims, dim);
+    const size_t lds = std::max<size_t>(TP_SCRATCH + 8 * (size_t)dim, 4 * A.samples * T);
+    if (lds > TP_LDS_MAX) return (int)hipErrorInvalidValue;
+    if (vt == VT_FLOAT) {
+        hipLaunchKernelGGL(tpt_rule_kernel<float>, dim3(A.nseg), dim3(TP_THREADS), lds, nullptr,
+                           (const float*)vectors, dim, A);
+        hipLaunchKernelGGL(tpt_side_kernel<float>, dim3(A.nitems), dim3(TP_THREADS), 0, nullptr,
+                           (const float*)vectors, dim, A);
+    } else {
+        hipLaunchKernelGGL(tpt_rule_kernel<int8_t>, dim3(A.nseg), dim3(TP_THREADS), lds, nullptr,
+                           (const int8_t*)vectors, dim, A);
+        hipLaunchKernelGGL(tpt_side_kernel<int8_t>, dim3(A.nitems), dim3(TP_THREADS), 0, nullptr,
+                           (const int8_t*)vectors, dim, A);
+    }
+    hipLaunchKernelGGL(tpt_scan_kernel, dim3(A.nseg), dim3(64), 0, nullptr, A);
+    hipLaunchKernelGGL(tpt_scatter_kernel, dim3(A.nitems), dim3(TP_THREADS), 0, nullptr, A);
     return (int)hipGetLastError();
 }
 

@@ -1412,6 +1412,175 @@ int sptag_amd_kmeans_assign(SptagAmdIndex* ix, const int32_t* members, int32_t n
     return SPTAG_AMD_OK;
 }
 
+/* What both TP-tree-partition entries can check from the host. */
+static bool tpt_args_ok(const void* members, int32_t nmembers, int32_t leaf_size,
+                        int32_t samples, int32_t topdims, int32_t trials,
+                        const void* out_members, const void* out_starts, const void* out_counts,
+                        int32_t max_leaves, const void* out_nleaves)
+{
+    return members && out_members && out_starts && out_counts && out_nleaves && nmembers >= 1 &&
+           leaf_size >= 1 && samples >= 1 && samples <= TPT_MAX_SAMPLES && topdims >= 1 &&
+           topdims <= TPT_MAX_DIMS && trials >= 0 && trials <= TPT_MAX_TRIALS && max_leaves >= 0;
+}
+
+/* TP-tree partition of a device member list, arguments checked; `device` is
+ * current. The level loop: the open segments of a level are split by one
+ * launch_tpt_level, the host reads their left counts back and cuts the next
+ * level's segments, the leaves and the items. A segment splits into two
+ * non-empty, strictly shorter ones, so the loop ends; it is bounded by
+ * nmembers levels all the same. d_out_members (which may be d_members) is
+ * written after the last level. */
+static int tpt_partition_core(const void* d_vectors, int vt, int32_t dim,
+                              const int32_t* d_members, int32_t nmembers, int32_t leaf_size,
+                              int32_t samples, int32_t topdims, int32_t trials, uint64_t seed,
+                              int32_t* d_out_members, int32_t* out_starts, int32_t* out_counts,
+                              int32_t max_leaves, int32_t* out_nleaves)
+{
+    struct Open { int32_t first, count; };
+    std::vector<Open> open, next_open;
+    std::vector<std::pair<int32_t, int32_t>> leaves;    /* (start, count) */
+    if (nmembers <= leaf_size) leaves.push_back({0, nmembers});
+    else open.push_back({0, nmembers});
+
+    const size_t maxseg = std::max<size_t>((size_t)nmembers / ((size_t)leaf_size + 1), 1);
+    const size_t maxitems = (size_t)nmembers / TPT_ITEM + maxseg;
+    DevBuf d_a, d_b, d_fin, d_codes, d_segs, d_items, d_rules, d_il, d_ib, d_sl;
+    if (!open.empty()) {
+        const size_t lb = (size_t)nmembers * 4;
+        HIP_OR_FAIL(d_a.alloc(lb), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_b.alloc(lb), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_fin.alloc(lb), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_codes.alloc(lb), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_segs.alloc(maxseg * sizeof(TptSeg)), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_rules.alloc(maxseg * sizeof(TptRule)), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_sl.alloc(maxseg * 4), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_items.alloc(maxitems * sizeof(TptItem)), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_il.alloc(maxitems * 4), SPTAG_AMD_ERR_OOM);
+        HIP_OR_FAIL(d_ib.alloc(maxitems * 4), SPTAG_AMD_ERR_OOM);
+    }
+    TptArgs A = {};
+    A.cur = d_members;
+    A.next = d_a.as<int32_t>();
+    A.fin = d_fin.as<int32_t>();
+    A.segs = d_segs.as<TptSeg>();
+    A.items = d_items.as<TptItem>();
+    A.leaf_size = leaf_size;
+    A.samples = samples;
+    A.topdims = topdims;
+    A.trials = trials;
+    A.seed = seed;
+    A.rules = d_rules.as<TptRule>();
+    A.codes = d_codes.as<int32_t>();
+    A.item_left = d_il.as<int32_t>();
+    A.item_base = d_ib.as<int32_t>();
+    A.seg_left = d_sl.as<int32_t>();
+    std::vector<TptSeg> segs;
+    std::vector<TptItem> items;
+    std::vector<int32_t> lefts;
+    for (int32_t level = 0; !open.empty(); level++) {
+        if (level >= nmembers || open.size() > maxseg) return SPTAG_AMD_ERR_INTERNAL;
+        segs.clear();
+        items.clear();
+        for (const Open& o : open) {
+            const int32_t item0 = (int32_t)items.size();
+            for (int32_t p = 0; p < o.count; p += TPT_ITEM)
+                items.push_back({(int32_t)segs.size(), o.first + p,
+                                 std::min<int32_t>(TPT_ITEM, o.count - p), p});
+            segs.push_back({o.first, o.count, level, item0, (int32_t)items.size() - item0});
+        }
+        if (items.size() > maxitems) return SPTAG_AMD_ERR_INTERNAL;
+        HIP_OR_FAIL(hipMemcpy(d_segs.as(), segs.data(), segs.size() * sizeof(TptSeg),
+                              hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
+        HIP_OR_FAIL(hipMemcpy(d_items.as(), items.data(), items.size() * sizeof(TptItem),
+                              hipMemcpyHostToDevice), SPTAG_AMD_ERR_NOGPU);
+        A.nseg = (int32_t)segs.size();
+        A.nitems = (int32_t)items.size();
+        int err = launch_tpt_level(vt, d_vectors, dim, A);
+        if (err != 0) {
+            fprintf(stderr, "sptag_amd: tpt partition launch failed %d\n", err);
+            return SPTAG_AMD_ERR_INTERNAL;
+        }
+        lefts.resize(segs.size());
+        HIP_OR_FAIL(hipMemcpy(lefts.data(), d_sl.as(), segs.size() * 4, hipMemcpyDeviceToHost),
+                    SPTAG_AMD_ERR_NOGPU);
+        next_open.clear();
+        for (size_t s = 0; s < open.size(); s++) {
+            const int32_t c = open[s].count, l = lefts[s];
+            if (l < 0 || l > c) return SPTAG_AMD_ERR_INTERNAL;
+            const int32_t nl = (l == 0 || l == c) ? c / 2 : l;     /* the rank cut */
+            const Open kids[2] = {{open[s].first, nl}, {open[s].first + nl, c - nl}};
+            for (const Open& k : kids) {
+                if (k.count <= leaf_size) leaves.push_back({k.first, k.count});
+                else next_open.push_back(k);
+            }
+        }
+        open.swap(next_open);
+        A.cur = A.next;
+        A.next = A.cur == d_a.as<int32_t>() ? d_b.as<int32_t>() : d_a.as<int32_t>();
+    }
+    std::sort(leaves.begin(), leaves.end());
+    if (leaves.size() > (size_t)max_leaves) {
+        *out_nleaves = (int32_t)leaves.size();
+        return SPTAG_AMD_ERR_PARAM;
+    }
+    const int32_t* src = d_fin ? d_fin.as<int32_t>() : d_members;
+    if (src != d_out_members)
+        HIP_OR_FAIL(hipMemcpy(d_out_members, src, (size_t)nmembers * 4,
+                              hipMemcpyDeviceToDevice), SPTAG_AMD_ERR_NOGPU);
+    HIP_OR_FAIL(hipDeviceSynchronize(), SPTAG_AMD_ERR_NOGPU);
+    for (size_t i = 0; i < leaves.size(); i++) {
+        out_starts[i] = leaves[i].first;
+        out_counts[i] = leaves[i].second;
+    }
+    *out_nleaves = (int32_t)leaves.size();
+    return SPTAG_AMD_OK;
+}
+
+int sptag_amd_tpt_partition_device(int device, const void* d_vectors, int valuetype, int32_t n,
+                                   int32_t dim, const int32_t* d_members, int32_t nmembers,
+                                   int32_t leaf_size, int32_t samples, int32_t topdims,
+                                   int32_t trials, uint64_t seed, int32_t* d_out_members,
+                                   int32_t* out_leaf_starts, int32_t* out_leaf_counts,
+                                   int32_t max_leaves, int32_t* out_nleaves)
+{
+    if (!d_vectors || n < 1 || dim < 1 || dim > MAX_DIM ||
+        (valuetype != VT_FLOAT && valuetype != VT_INT8) ||
+        (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) ||
+        !tpt_args_ok(d_members, nmembers, leaf_size, samples, topdims, trials, d_out_members,
+                     out_leaf_starts, out_leaf_counts, max_leaves, out_nleaves))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    return tpt_partition_core(d_vectors, valuetype, dim, d_members, nmembers, leaf_size, samples,
+                              topdims, trials, seed, d_out_members, out_leaf_starts,
+                              out_leaf_counts, max_leaves, out_nleaves);
+}
+
+int sptag_amd_tpt_partition(SptagAmdIndex* ix, const int32_t* members, int32_t nmembers,
+                            int32_t leaf_size, int32_t samples, int32_t topdims, int32_t trials,
+                            uint64_t seed, int32_t* out_members, int32_t* out_leaf_starts,
+                            int32_t* out_leaf_counts, int32_t max_leaves, int32_t* out_nleaves)
+{
+    if (!ix || !tpt_args_ok(members, nmembers, leaf_size, samples, topdims, trials, out_members,
+                            out_leaf_starts, out_leaf_counts, max_leaves, out_nleaves))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available() || !ix->d_vectors) return SPTAG_AMD_ERR_NOGPU;
+    std::lock_guard<std::mutex> g(ix->lock);
+    for (int32_t i = 0; i < nmembers; i++)
+        if (members[i] < 0 || members[i] >= ix->n) return SPTAG_AMD_ERR_PARAM;
+    HIP_OR_FAIL(hipSetDevice(ix->device), SPTAG_AMD_ERR_NOGPU);
+    DevBuf d_mem;
+    int rc = dev_upload(d_mem, members, (size_t)nmembers * 4);
+    if (rc != SPTAG_AMD_OK) return rc;
+    rc = tpt_partition_core(ix->d_vectors.as(), ix->vt, ix->dim, d_mem.as<int32_t>(), nmembers,
+                            leaf_size, samples, topdims, trials, seed, d_mem.as<int32_t>(),
+                            out_leaf_starts, out_leaf_counts, max_leaves, out_nleaves);
+    if (rc != SPTAG_AMD_OK) return rc;
+    HIP_OR_FAIL(hipMemcpy(out_members, d_mem.as(), (size_t)nmembers * 4, hipMemcpyDeviceToHost),
+                SPTAG_AMD_ERR_NOGPU);
+    return SPTAG_AMD_OK;
+}
+
 /* Host-side distance restatements for the add path's edge arithmetic
  * (RebuildNeighbors / InsertNeighbors recompute pair distances on the
  * host, as the reference does on CPU): same rounding contracts as the
