@@ -171,6 +171,43 @@ int sptag_amd_group_knn_device(int device, const void* d_vectors, int valuetype,
                                int32_t ngroups, int32_t k, int32_t* d_out_vids,
                                float* d_out_dists);
 
+/* Grouped exact kNN with a choice of selection. The result is that of
+ * sptag_amd_group_knn[_device] in every byte, whatever the selection; the
+ * arguments are theirs, with `selection` before k, and so are the checks.
+ *   SPTAG_AMD_GK_STREAM  the two calls above: rows stream past a threshold
+ *                        and survivors are merged into the list 32 at a
+ *                        time. Made for few survivors (exact search's shape).
+ *   SPTAG_AMD_GK_SORT    every distance of a query to its group goes into a
+ *                        row of an LDS matrix; one wave then radix-selects
+ *                        the k-th (dist, vid), compacts the survivors and
+ *                        sorts them once. Made for leaf-sized groups, where k
+ *                        is a sizeable part of the group. Groups of at most
+ *                        sptag_amd_group_knn_sort_max(valuetype, dim)
+ *                        members; SPTAG_AMD_ERR_PARAM, outputs untouched, if
+ *                        any group is larger.
+ *   SPTAG_AMD_GK_AUTO    per group, the selection that was measured faster
+ *                        for its size and k; larger groups
+ *                        stream, in the same call. Never fails for size.
+ * Any other selection is SPTAG_AMD_ERR_PARAM. */
+#define SPTAG_AMD_GK_STREAM 0
+#define SPTAG_AMD_GK_SORT 1
+#define SPTAG_AMD_GK_AUTO 2
+int sptag_amd_group_knn_sel(SptagAmdIndex* idx, const int32_t* members, int32_t nmembers,
+                            const int32_t* starts, const int32_t* counts, int32_t ngroups,
+                            int32_t selection, int32_t k, int32_t* out_vids,
+                            float* out_dists);
+int sptag_amd_group_knn_sel_device(int device, const void* d_vectors, int valuetype,
+                                   int distmethod, int32_t n, int32_t dim,
+                                   const int32_t* d_members, int32_t nmembers,
+                                   const int32_t* starts, const int32_t* counts,
+                                   int32_t ngroups, int32_t selection, int32_t k,
+                                   int32_t* d_out_vids, float* d_out_dists);
+/* The largest group SPTAG_AMD_GK_SORT takes for a value type and dim: what
+ * 160 KiB of LDS leave for a 32-query distance matrix beside the distance
+ * tiles, a multiple of 64, at most 1024 (1024 at f32 dim 128 and int8 dim
+ * 100). 0 for a value type or dim that the grouped calls reject. */
+int32_t sptag_amd_group_knn_sort_max(int valuetype, int32_t dim);
+
 /* RNG prune: the reference's RebuildNeighbors rule
  * (RelativeNeighborhoodGraph.h:18-35) over caller-supplied candidate lists,
  * the step that ends every graph stage of the index builder. Row r has a node

@@ -8,7 +8,9 @@ stream, alternating for --rounds rounds of --reps calls after one warm-up
 each:
 
   hip     build._leaf_knn_hip: sptag_amd.group_knn_device on the vectors'
-          own device buffer, plus the builder's padding conventions
+          own device buffer, plus the builder's padding conventions, once
+          for every --selection given ("stream", "sort", "auto"), all in the
+          same rounds; their outputs are compared for equal bytes first
   torch   build._leaf_knn, the padded [B, m, m] GEMM-identity + topk step
 
 and the peak extra device memory of one call of each
@@ -68,9 +70,16 @@ def f32_workload(args, torch, build):
     gen.manual_seed(2016)
     perm, starts, counts = build._tpt_leaves(xf, args.leaf, gen)
     say(f"{tag}: {counts.numel()} leaves of {int(counts.min())}..{int(counts.max())} rows")
-    hip = lambda: build._leaf_knn_hip(xf, perm, starts, counts, args.k)
+    hips = {s: (lambda s=s: build._leaf_knn_hip(xf, perm, starts, counts, args.k, s))
+            for s in args.selection}
+    hip = hips[args.selection[0]]
     tor = lambda: build._leaf_knn(xf, perm, starts, counts, args.k)
     hv, hd = hip()          # warm-up, and the outputs to compare
+    for s in args.selection[1:]:
+        sv, sd = hips[s]()
+        say(f"{tag}: {s} equals {args.selection[0]} in every byte: "
+            f"{bool((sv == hv).all() and (sd.view(torch.int32) == hd.view(torch.int32)).all())}")
+        del sv, sd
     tv, td = tor()
     say(f"{tag}: rows whose id lists differ: {int((hv != tv).any(1).sum())} of {args.n}; "
         f"largest relative distance difference "
@@ -79,18 +88,22 @@ def f32_workload(args, torch, build):
     say(f"{tag}: peak extra device memory: hip {peak_extra(torch, hip) / 2**20:.0f} MiB "
         f"(the [n, k] outputs and the int32 members), torch "
         f"{peak_extra(torch, tor) / 2**20:.0f} MiB")
-    th, tt = [], []
+    th, tt = {s: [] for s in hips}, []
     for rnd in range(args.rounds):
-        h = event_ms(torch, hip, args.reps)
+        line = []
+        for s, fn in hips.items():
+            h = event_ms(torch, fn, args.reps)
+            th[s] += h
+            line.append(f"hip {s} median {statistics.median(h):.2f} ms")
         t = event_ms(torch, tor, args.reps)
-        th += h
         tt += t
-        say(f"{tag}: round {rnd}: hip median {statistics.median(h):.2f} ms, torch median "
+        say(f"{tag}: round {rnd}: {', '.join(line)}, torch median "
             f"{statistics.median(t):.2f} ms")
-    mh, sh = summary(tag, "hip", th)
     mt, st = summary(tag, "torch", tt)
-    say(f"{tag}: torch / hip = {mt / mh:.2f}; torch - hip = {mt - mh:.2f} ms against the "
-        f"two spreads combined {sh + st:.2f} ms")
+    for s in hips:
+        mh, sh = summary(tag, f"hip {s}", th[s])
+        say(f"{tag}: torch / hip {s} = {mt / mh:.2f}; torch - hip {s} = {mt - mh:.2f} ms "
+            f"against the two spreads combined {sh + st:.2f} ms")
 
 
 def i8_workload(args, torch, sptag_amd, build):
@@ -102,9 +115,11 @@ def i8_workload(args, torch, sptag_amd, build):
     perm, starts, counts = build._tpt_leaves(torch.from_numpy(x).to("cuda:0").float(),
                                              args.leaf, gen)
     perm, starts, counts = (a.cpu().numpy().astype(np.int32) for a in (perm, starts, counts))
-    fn = lambda: ix.GroupKnn(perm, starts, counts, args.k)
-    fn()
-    summary(tag, "hip, handle form with its copies", event_ms(torch, fn, args.rounds * args.reps))
+    for s in args.selection:
+        fn = lambda: ix.GroupKnn(perm, starts, counts, args.k, selection=s)
+        fn()
+        summary(tag, f"hip {s}, handle form with its copies",
+                event_ms(torch, fn, args.rounds * args.reps))
 
 
 def main():
@@ -114,6 +129,9 @@ def main():
     ap.add_argument("--k", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--selection", nargs="+", default=["stream"],
+                    choices=["stream", "sort", "auto"])
+    ap.add_argument("--skip-i8", action="store_true")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.out:
@@ -125,7 +143,8 @@ def main():
         sys.exit("group_knn_bench.py needs a HIP device")
     say(f"device: {torch.cuda.get_device_name(0)}")
     f32_workload(args, torch, build)
-    i8_workload(args, torch, sptag_amd, build)
+    if not args.skip_i8:
+        i8_workload(args, torch, sptag_amd, build)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["AnnIndex", "ShardedIndex", "merge_topk", "group_knn_device",
-           "rng_prune_device", "pool_join_device", "kmeans_assign_device",
+           "group_knn_sort_max", "rng_prune_device", "pool_join_device", "kmeans_assign_device",
            "tpt_partition_device",
            "MetadataSet", "load_library", "gpu_available", "SptagAmdError"]
 
@@ -89,6 +89,17 @@ def load_library():
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
         ctypes.c_void_p, ctypes.c_void_p]
+    # the _sel forms take `selection` before k
+    lib.sptag_amd_group_knn_sel.restype = ctypes.c_int
+    lib.sptag_amd_group_knn_sel.argtypes = (
+        lib.sptag_amd_group_knn.argtypes[:6] + [ctypes.c_int32] +
+        lib.sptag_amd_group_knn.argtypes[6:])
+    lib.sptag_amd_group_knn_sel_device.restype = ctypes.c_int
+    lib.sptag_amd_group_knn_sel_device.argtypes = (
+        lib.sptag_amd_group_knn_device.argtypes[:11] + [ctypes.c_int32] +
+        lib.sptag_amd_group_knn_device.argtypes[11:])
+    lib.sptag_amd_group_knn_sort_max.restype = ctypes.c_int32
+    lib.sptag_amd_group_knn_sort_max.argtypes = [ctypes.c_int, ctypes.c_int32]
     lib.sptag_amd_rng_prune.restype = ctypes.c_int
     lib.sptag_amd_rng_prune.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
@@ -401,12 +412,17 @@ class AnnIndex:
         if rc != 0:
             raise SptagAmdError(rc, "exact_search_device")
 
-    def GroupKnn(self, members, starts, counts, k):
+    def GroupKnn(self, members, starts, counts, k, selection="stream"):
         """Exact kNN inside row groups: group g is members[starts[g] :
         starts[g] + counts[g]] (vector ids, any order, none twice). Returns
         (vids int32 [n,k], dists f32 [n,k]) indexed by vector id: the k
         nearest OTHER members of the id's group, ascending (dist, vid),
-        vid=-1 padding; all padding for an id in no group."""
+        vid=-1 padding; all padding for an id in no group. selection picks the
+        kernel, never the result: "stream" (a threshold and merges), "sort"
+        (all distances of a query in LDS, one select and one sort; groups up
+        to group_knn_sort_max members, larger ones are an error) or "auto"
+        (per group, the one measured faster)."""
+        selection = _gk_selection(selection)
         members = np.ascontiguousarray(members, dtype=np.int32)
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         counts = np.ascontiguousarray(counts, dtype=np.int32)
@@ -416,9 +432,9 @@ class AnnIndex:
         vids = np.empty((n, k), dtype=np.int32)
         dists = np.empty((n, k), dtype=np.float32)
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        rc = self._lib.sptag_amd_group_knn(
+        rc = self._lib.sptag_amd_group_knn_sel(
             self._h, p(members), members.size, p(starts), p(counts),
-            starts.size, k, p(vids), p(dists))
+            starts.size, selection, k, p(vids), p(dists))
         if rc != 0:
             raise SptagAmdError(rc, "group_knn")
         return vids, dists
@@ -621,24 +637,40 @@ class AnnIndex:
             raise SptagAmdError(rc, "save_index")
 
 
+GK_SELECTIONS = {"stream": 0, "sort": 1, "auto": 2}
+
+
+def _gk_selection(selection):
+    if selection not in GK_SELECTIONS:
+        raise ValueError('selection must be "stream", "sort" or "auto"')
+    return GK_SELECTIONS[selection]
+
+
+def group_knn_sort_max(valuetype, dim):
+    """The largest group that selection="sort" takes for a value type
+    (VT_FLOAT / VT_INT8) and dim; 0 where grouped kNN rejects them."""
+    return int(load_library().sptag_amd_group_knn_sort_max(valuetype, dim))
+
+
 def group_knn_device(d_vectors_ptr, valuetype, distmethod, n, dim,
                      d_members_ptr, nmembers, starts, counts, k, d_vids_ptr,
-                     d_dists_ptr, device=0):
+                     d_dists_ptr, device=0, selection="stream"):
     """AnnIndex.GroupKnn without a handle, on HIP device addresses (e.g. torch
     tensors' .data_ptr()): vectors [n, dim] of `valuetype`, int32 members
     [nmembers], outputs int32 / float32 [n, k]. starts and counts are host
     arrays. The caller guarantees that every member is inside [0, n) and
-    occurs once."""
+    occurs once. selection as in AnnIndex.GroupKnn."""
+    selection = _gk_selection(selection)
     starts = np.ascontiguousarray(starts, dtype=np.int32)
     counts = np.ascontiguousarray(counts, dtype=np.int32)
     if starts.shape != counts.shape or starts.ndim != 1:
         raise ValueError("starts and counts must be 1-d and of one length")
     dm = {"L2": DM_L2, "Cosine": DM_COSINE}.get(distmethod, distmethod)
-    rc = load_library().sptag_amd_group_knn_device(
+    rc = load_library().sptag_amd_group_knn_sel_device(
         device, ctypes.c_void_p(d_vectors_ptr), valuetype, dm, n, dim,
         ctypes.c_void_p(d_members_ptr), nmembers,
         starts.ctypes.data_as(ctypes.c_void_p),
-        counts.ctypes.data_as(ctypes.c_void_p), starts.size, k,
+        counts.ctypes.data_as(ctypes.c_void_p), starts.size, selection, k,
         ctypes.c_void_p(d_vids_ptr), ctypes.c_void_p(d_dists_ptr))
     if rc != 0:
         raise SptagAmdError(rc, "group_knn_device")

@@ -613,11 +613,12 @@ def _leaf_knn(xf, perm, starts, counts, kper, chunk_rows=1_000_000):
     return ids, dst
 
 
-def _leaf_knn_hip(xf, perm, starts, counts, kper):
+def _leaf_knn_hip(xf, perm, starts, counts, kper, selection="stream"):
     """_leaf_knn by the grouped-kNN HIP kernels (sptag_amd.group_knn_device):
     the same shapes and padding, with the search path's f32 L2 distances
     in place of the |a|^2 + |b|^2 - 2ab identity, ties by id, and no padded
-    [B, m, m] tensor."""
+    [B, m, m] tensor. selection picks the kernels' selection, not the
+    result."""
     if xf.device.type != "cuda":
         raise RuntimeError('leaf_knn="hip" needs the vectors on a GPU, got '
                            f"device {xf.device}")
@@ -632,7 +633,7 @@ def _leaf_knn_hip(xf, perm, starts, counts, kper):
     group_knn_device(xf.data_ptr(), VT_FLOAT, DM_L2, n, d, members.data_ptr(),
                      members.numel(), starts.cpu().numpy(), counts.cpu().numpy(),
                      k, ids.data_ptr(), dst.data_ptr(),
-                     device=xf.device.index or 0)
+                     device=xf.device.index or 0, selection=selection)
     dst.masked_fill_(ids < 0, float("inf"))
     if k < kper:
         ids = torch.nn.functional.pad(ids, (0, kper - k), value=-1)
@@ -640,7 +641,13 @@ def _leaf_knn_hip(xf, perm, starts, counts, kper):
     return ids, dst
 
 
-_LEAF_KNN = {"torch": _leaf_knn, "hip": _leaf_knn_hip}
+def _leaf_knn_hip_sort(xf, perm, starts, counts, kper):
+    """_leaf_knn_hip with the sorted selection wherever it is the faster one
+    (selection="auto"): the same bytes."""
+    return _leaf_knn_hip(xf, perm, starts, counts, kper, selection="auto")
+
+
+_LEAF_KNN = {"torch": _leaf_knn, "hip": _leaf_knn_hip, "hip_sort": _leaf_knn_hip_sort}
 
 
 def _merge_candidates(ids_a, dst_a, ids_b, dst_b, cand, self_ids,
@@ -896,8 +903,10 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
     """Returns (graph, cand_ids, cand_dst), tensors on the device: graph
     int32 [n, degree] (RNG-pruned, ascending, -1 padded) and the [n, cand]
     candidate pools it was pruned from, which the refine steps grow.
-    leaf_knn: "torch" (padded GEMM + topk) or "hip" (the grouped-kNN
-    kernels; GPU only) for the exact KNN inside the TP-tree leaves.
+    leaf_knn: "torch" (padded GEMM + topk), "hip" (the grouped-kNN kernels,
+    streaming selection; GPU only) or "hip_sort" (the same kernels with the
+    sorted selection where it is faster: the same bytes as "hip") for the
+    exact KNN inside the TP-tree leaves.
     prune: "torch" (_rng_prune) or "hip" (the RNG-prune kernels; GPU only)
     for the RebuildNeighbors step.
     join: "torch" (_exact_l2 + _merge_candidates) or "hip" (the pool-join
@@ -907,7 +916,8 @@ def build_rng_graph(vectors, *, degree=32, ntrees=4, tpt_leaf=1000, cand=256,
     only; ragged leaves) for the partitions that make the leaves."""
     tpt_fn = _tpt_fn(tpt)
     if leaf_knn not in _LEAF_KNN:
-        raise ValueError(f'leaf_knn must be "torch" or "hip", got {leaf_knn!r}')
+        raise ValueError('leaf_knn must be "torch" or "hip" (or "hip_sort"), '
+                         f'got {leaf_knn!r}')
     prune_fn = _prune_fn(prune)
     join_fn = _join_fn(join)
     device, xf, gen = _prologue(vectors, device, seed + 77)

@@ -210,11 +210,20 @@ int launch_exact(int valuetype, int distmethod, const DevIndex& di,
  * is all padding. A workgroup owns one GroupTile: the EXACT_QT members of a
  * group from q0 on as queries, q0 a multiple of EXACT_QT below count. The
  * tiles cover every member of every group once. All pointers are device
- * memory; every member is inside [0, n). */
+ * memory; every member is inside [0, n).
+ * The table is in two parts: the first nsorted tiles belong to groups of at
+ * most sort_stride members and run the sorted selection (every distance of a
+ * query into an LDS row of sort_stride words, one radix select and one sort
+ * per query), the nstream tiles behind them the streaming selection; both
+ * write the same bytes. sort_stride is a multiple of 64, at most
+ * group_knn_sort_max(valuetype, dim), which is what gfx950's 160 KiB of LDS
+ * leave for the matrix (0 for arguments the kernels do not take). */
 struct GroupTile { int32_t start, count, q0; };
+int group_knn_sort_max(int valuetype, int32_t dim);
 int launch_group_knn(int valuetype, int distmethod, const void* vectors, int32_t n,
                      int32_t dim, const int32_t* members, const GroupTile* tiles,
-                     int32_t ntiles, int32_t k, int32_t* out_v, float* out_d);
+                     int32_t nsorted, int32_t sort_stride, int32_t nstream, int32_t k,
+                     int32_t* out_v, float* out_d);
 
 /* RNG prune (exact.hip): RebuildNeighbors over candidate lists. Row r walks
  * cand_ids[r][0..ncand) (ascending cand_dists, never recomputed) in order

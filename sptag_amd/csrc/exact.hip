@@ -92,6 +92,19 @@ DEV float wave_bcast(float v, int l)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
+/* An f32 as an unsigned key of the same order (negative distances included),
+ * -0 folded to +0; the pool join's keys and the sorted grouped selection's. */
+DEV uint32_t dist_key(float dist)
+{
+    const uint32_t b = dist == 0.0f ? 0u : (uint32_t)__float_as_int(dist);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+DEV float dist_unkey(uint32_t b)
+{
+    return __int_as_float((int)((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b));
+}
+
 /* One wave merges n <= 64 candidates (any order, keys distinct from the
  * list's) into the sorted list lv/ld of k entries, in place. The new place of
  * a list entry is its index plus the candidates before it, of a candidate
@@ -783,7 +796,39 @@ void exact_i8_kernel(DevIndex di, const int8_t* __restrict__ queries, int32_t nq
  *           dist <= thr: keys are distinct, a row whose key is above the
  *           k-th falls out in the merge, which ranks by (dist, vid).
  *   self    The pair (v, v) is skipped by vid; another vid with the same
- *           vector is a neighbour at its distance. */
+ *           vector is a neighbour at its distance.
+ *
+ * That is the streaming selection (SORTED = false). A leaf of the index
+ * builder is the opposite of exact search's shape: about 1000 rows, k a
+ * sizeable part of them, a threshold that never gets tight, so most rows cost
+ * a merge. The sorted selection (SORTED = true, groups of at most
+ * group_knn_sort_max members) runs the same distance phase and no admission
+ * at all:
+ *
+ *   matrix  Every distance of the tile goes, as f32 bits, to mat[query][row
+ *           position] in LDS; the self pair, and a distance the streaming
+ *           form would never admit (above MaxDist, NaN), is stored as
+ *           GK_WORST. The member ids of the whole group sit in LDS beside it,
+ *           so a position gives its vid.
+ *   select  After the last tile a wave takes the queries wave, wave + 4, ..
+ *           one at a time. The query's row goes to registers as dist_key's
+ *           (position lane + 64 j in register j), a bitwise radix descent
+ *           with ballots finds the k-th smallest distance key, and if more
+ *           rows tie there than are wanted a second descent over the vids of
+ *           the ties finds the last vid to take: members come in any order.
+ *           The at most k survivors are compacted by ballot, keys into the
+ *           query's own row, whose values are all in registers by then, vids
+ *           into the wave's scratch, which lies over the row and query tiles
+ *           that the distance phase is done with.
+ *   sort    Up to 64 survivors are ranked in registers (readlane, as
+ *           merge_cands does); more by a bitonic network over the two LDS
+ *           arrays in its always-ascending form, in which a pair whose upper
+ *           index is past the survivors is a no-op, so nothing is padded to a
+ *           power of two. Then the row is written; group_fill_kernel has
+ *           padded it already.
+ *
+ * The same (dist, vid) order decides both selections, so they write the same
+ * bytes. */
 
 struct GrpLds { uint32_t qvid, mids, total; };
 
@@ -818,20 +863,198 @@ DEV int group_queries(const GroupTile& T, const int32_t* __restrict__ members, i
     return nql;
 }
 
-template <int DM, bool QRES>
+/* The sorted selection's LDS: gfx950 gives a workgroup up to 160 KiB, and the
+ * matrix takes what the launch's largest group needs of it. */
+enum { GK_SORT_CAP = 1024, GK_LDS_MAX = 160 * 1024, GK_WORST = 0x7fffffff };
+static constexpr uint32_t GK_KEY_WORST = 0xffffffffu;      /* dist_key of GK_WORST */
+static_assert(GK_SORT_CAP <= MAX_K && GK_SORT_CAP % 64 == 0, "a row is whole 64-lane chunks");
+
+struct SrtLds { uint32_t scratch, qvid, mids, gids, mat, total; };
+
+/* tile_bytes: the distance phase's regions (query tile, row tiles, self-dots:
+ * everything below `thr` of the exact kernels' layout), which the selection
+ * reuses as XWAVES x stride words of scratch; rt: rows of a tile; stride: the
+ * matrix's row stride in words, a multiple of 64 that covers every group of
+ * the launch. */
+static inline __host__ __device__ SrtLds srt_lds(uint32_t tile_bytes, int rt, int stride)
+{
+    SrtLds l;
+    const uint32_t scratch = (uint32_t)XWAVES * stride * 4;
+    uint32_t b = tile_bytes > scratch ? tile_bytes : scratch;
+    l.scratch = 0;
+    l.qvid = b; b += XQT * 4;
+    l.mids = b; b += 2 * rt * 4;
+    l.gids = b; b += (uint32_t)stride * 4;
+    l.mat = b;  b += (uint32_t)XQT * stride * 4;
+    l.total = b;
+    return l;
+}
+
+/* what goes into the matrix for a pair: `other` is false for the self pair */
+DEV uint32_t srt_bits(float dist, bool other)
+{
+    return (other && dist <= MAXDIST) ? (uint32_t)__float_as_int(dist) : (uint32_t)GK_WORST;
+}
+
+/* Orders a wave's LDS accesses against those of its other lanes: a wave's
+ * LDS operations are carried out in issue order, so this only has to stop
+ * the compiler moving or forwarding accesses across it. */
+DEV void srt_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+/* One wave selects and writes one query's row. row: the query's `count`
+ * distances as f32 bits (destroyed); gids: the group's member ids by
+ * position; sv: the wave's scratch, as long as a row; ov/od: the output row,
+ * all padding. NCH: 64-lane chunks that cover count. */
+template <int NCH>
+DEV void srt_select(uint32_t* row, const int32_t* gids, uint32_t* sv, int count, int k,
+                    int32_t* ov, float* od)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t key[NCH];
+    int m = 0;          /* rows that may be taken at all */
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+        const int pos = j * 64 + lane;
+        key[j] = pos < count ? dist_key(__int_as_float((int)row[pos])) : GK_KEY_WORST;
+        m += __popcll(__ballot(key[j] != GK_KEY_WORST));
+    }
+    const int kk = min(k, m);
+    if (kk == 0) return;
+
+    /* taken: key < P, or key == P with vid <= Q. With kk == m that is every
+     * valid key: they are all below dist_key(MaxDist). */
+    uint32_t P = GK_KEY_WORST - 1, Q = 0x7fffffffu;
+    if (kk < m) {
+        P = 0;      /* the largest P with fewer than kk keys below it: the kk-th smallest */
+        for (int b = 31; b >= 0; b--) {
+            const uint32_t trial = P | (1u << b);
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < NCH; j++) c += __popcll(__ballot(key[j] < trial));
+            if (c < kk) P = trial;
+        }
+        int less = 0, eq = 0;
+#pragma unroll
+        for (int j = 0; j < NCH; j++) {
+            less += __popcll(__ballot(key[j] < P));
+            eq += __popcll(__ballot(key[j] == P));
+        }
+        const int need = kk - less;     /* >= 1 of the eq ties */
+        if (eq > need) {                /* the need-th smallest vid among them */
+            uint32_t tv[NCH];
+#pragma unroll
+            for (int j = 0; j < NCH; j++)
+                tv[j] = key[j] == P ? (uint32_t)gids[j * 64 + lane] : 0xffffffffu;
+            Q = 0;
+            for (int b = 30; b >= 0; b--) {
+                const uint32_t trial = Q | (1u << b);
+                int c = 0;
+#pragma unroll
+                for (int j = 0; j < NCH; j++) c += __popcll(__ballot(tv[j] < trial));
+                if (c < need) Q = trial;
+            }
+        }
+    }
+
+    srt_fence();        /* the previous query's reads of sv are behind us */
+    int base = 0;
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+        const int pos = j * 64 + lane;
+        const uint32_t v = key[j] != GK_KEY_WORST ? (uint32_t)gids[pos] : 0u;
+        const bool take = key[j] < P || (key[j] == P && v <= Q);
+        const uint64_t mask = __ballot(take);
+        if (take) {
+            const int p = base + __popcll(mask & below);
+            row[p] = key[j];
+            sv[p] = v;
+        }
+        base += __popcll(mask);
+    }
+    srt_fence();
+
+    if (kk <= 64) {     /* one survivor to a lane: its rank is its place */
+        const uint32_t dk = lane < kk ? row[lane] : GK_KEY_WORST;
+        const uint32_t dv = lane < kk ? sv[lane] : 0xffffffffu;
+        int rank = 0;
+        for (int j = 0; j < kk; j++) {
+            const uint32_t jk = (uint32_t)__builtin_amdgcn_readlane((int)dk, j);
+            const uint32_t jv = (uint32_t)__builtin_amdgcn_readlane((int)dv, j);
+            rank += jk < dk || (jk == dk && jv < dv);
+        }
+        if (lane < kk) {
+            ov[rank] = (int32_t)dv;
+            od[rank] = dist_unkey(dk);
+        }
+        return;
+    }
+
+    int P2 = 128;
+    while (P2 < kk) P2 <<= 1;
+    for (int size = 2; size <= P2; size <<= 1) {
+        const int half = size >> 1;
+        for (int s = half; s > 0; s >>= 1) {
+            for (int i = lane; i < (P2 >> 1); i += 64) {
+                int lo, hi;
+                if (s == half) {    /* the stage's first step mirrors the upper half */
+                    const int r = i & (half - 1);
+                    lo = 2 * (i - r) + r;
+                    hi = 2 * (i - r) + size - 1 - r;
+                } else {
+                    lo = 2 * i - (i & (s - 1));
+                    hi = lo + s;
+                }
+                if (hi >= kk) continue;
+                const uint32_t ak = row[lo], bk = row[hi], av = sv[lo], bv = sv[hi];
+                if (bk < ak || (bk == ak && bv < av)) {
+                    row[lo] = bk; row[hi] = ak;
+                    sv[lo] = bv;  sv[hi] = av;
+                }
+            }
+            srt_fence();
+        }
+    }
+    for (int i = lane; i < kk; i += 64) {
+        ov[i] = (int32_t)sv[i];
+        od[i] = dist_unkey(row[i]);
+    }
+}
+
+/* After the distance phase's last barrier: every wave selects its queries. */
+DEV void srt_select_tile(unsigned char* lds, const SrtLds& S, int stride, const int32_t* qvid,
+                         int nql, int count, int k, int32_t* out_v, float* out_d)
+{
+    const int wave = threadIdx.x >> 6;
+    uint32_t* mat = (uint32_t*)(lds + S.mat);
+    const int32_t* gids = (const int32_t*)(lds + S.gids);
+    uint32_t* sv = (uint32_t*)(lds + S.scratch) + wave * stride;
+    for (int ql = wave; ql < nql; ql += XWAVES) {
+        uint32_t* row = mat + ql * stride;
+        int32_t* ov = out_v + (size_t)qvid[ql] * k;
+        float* od = out_d + (size_t)qvid[ql] * k;
+        if (count <= 64) srt_select<1>(row, gids, sv, count, k, ov, od);
+        else if (count <= 256) srt_select<4>(row, gids, sv, count, k, ov, od);
+        else srt_select<GK_SORT_CAP / 64>(row, gids, sv, count, k, ov, od);
+    }
+}
+
+/* sstride: the sorted selection's matrix stride (SORTED only) */
+template <int DM, bool QRES, bool SORTED>
 __global__ __launch_bounds__(XTHREADS, 2)
 void group_f32_kernel(const float* __restrict__ vectors, int d,
                       const int32_t* __restrict__ members,
-                      const GroupTile* __restrict__ tiles, int32_t k, int32_t* out_v,
-                      float* out_d)
+                      const GroupTile* __restrict__ tiles, int32_t k, int sstride,
+                      int32_t* out_v, float* out_d)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
     const F32Lds L = f32_lds(d);
     const GrpLds G = grp_lds(L.total, FRT);
+    const SrtLds S = srt_lds(L.thr, FRT, sstride);
     float* qlds = (float*)(xlds + L.q);
     float* rlds = (float*)(xlds + L.rows);
-    int32_t* qvid = (int32_t*)(xlds + G.qvid);
-    int32_t* mids = (int32_t*)(xlds + G.mids);     /* [2][FRT], by tile parity */
+    int32_t* qvid = (int32_t*)(xlds + (SORTED ? S.qvid : G.qvid));
+    int32_t* mids = (int32_t*)(xlds + (SORTED ? S.mids : G.mids));     /* [2][FRT], by tile parity */
     const int tid = threadIdx.x;
     const int g = tid & 15, gq = (tid >> 4) & 3, gr = tid >> 6, lr = tid >> 4;
     const GroupTile T = tiles[blockIdx.x];
@@ -862,7 +1085,12 @@ void group_f32_kernel(const float* __restrict__ vectors, int d,
         qid0 = qvid[lr];
         qid1 = qvid[16 + lr];
     }
-    sel_init(sel);
+    if constexpr (SORTED) {
+        int32_t* gids = (int32_t*)(xlds + S.gids);
+        for (int i = tid; i < T.count; i += XTHREADS) gids[i] = mem[i];
+    } else {
+        sel_init(sel);
+    }
 
     const int nslab = (d + FKS - 1) / FKS;
     const int ntile = (T.count + FRT - 1) / FRT;
@@ -909,15 +1137,25 @@ void group_f32_kernel(const float* __restrict__ vectors, int d,
             uint32_t pend = 0;
             const int32_t myvid = mids[(tile & 1) * FRT + gr * FMR + (g & 3)];
             f32_fold<DM>(acc, qb, rb, qstride, slab, d, g, dist);
+            if constexpr (SORTED) {
+                uint32_t* col = (uint32_t*)(xlds + S.mat) + tile * FRT + gr * FMR + (g & 3);
 #pragma unroll
-            for (int i = 0; i < FMQ; i++) {
-                ql[i] = gq + 4 * i;
-                vid[i] = myvid;
-                if (g < FMR && myvid >= 0 && ql[i] < nql && myvid != qvid[ql[i]] &&
-                    dist[i] <= sel.thr[ql[i]])
-                    pend |= 1u << i;
+                for (int i = 0; i < FMQ; i++) {
+                    const int q = gq + 4 * i;
+                    if (g < FMR && myvid >= 0 && q < nql)
+                        col[q * sstride] = srt_bits(dist[i], myvid != qvid[q]);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < FMQ; i++) {
+                    ql[i] = gq + 4 * i;
+                    vid[i] = myvid;
+                    if (g < FMR && myvid >= 0 && ql[i] < nql && myvid != qvid[ql[i]] &&
+                        dist[i] <= sel.thr[ql[i]])
+                        pend |= 1u << i;
+                }
+                sel_append(sel, pend, dist, ql, vid);
             }
-            sel_append(sel, pend, dist, ql, vid);
         }
 
         if (more) {
@@ -932,27 +1170,31 @@ void group_f32_kernel(const float* __restrict__ vectors, int d,
         tile = ntl;
         slab = nsl;
     }
-    flush_cands(sel, 1);
+    if constexpr (SORTED)
+        srt_select_tile(xlds, S, sstride, qvid, nql, T.count, k, out_v, out_d);
+    else
+        flush_cands(sel, 1);
 }
 
 enum { GI_CPR_MAX = (I_MAX_W + 3) / 4,      /* 16-byte chunks of a row at the dim guard */
        GI_NCH = (IRT * GI_CPR_MAX + XTHREADS - 1) / XTHREADS };  /* chunks per thread */
 
-template <int DM>
+template <int DM, bool SORTED>
 __global__ __launch_bounds__(XTHREADS, 2)
 void group_i8_kernel(const int8_t* __restrict__ vectors, int d,
                      const int32_t* __restrict__ members,
-                     const GroupTile* __restrict__ tiles, int32_t k, int32_t* out_v,
-                     float* out_d)
+                     const GroupTile* __restrict__ tiles, int32_t k, int sstride,
+                     int32_t* out_v, float* out_d)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
     const I8Lds L = i8_lds(d);
     const GrpLds G = grp_lds(L.total, IRT);
+    const SrtLds S = srt_lds(L.thr, IRT, sstride);
     uint32_t* qlds = (uint32_t*)(xlds + L.q);
     uint32_t* rlds = (uint32_t*)(xlds + L.rows);
     int* aa = (int*)(xlds + L.aa);
-    int32_t* qvid = (int32_t*)(xlds + G.qvid);
-    int32_t* mids = (int32_t*)(xlds + G.mids);     /* [2][IRT], by tile parity */
+    int32_t* qvid = (int32_t*)(xlds + (SORTED ? S.qvid : G.qvid));
+    int32_t* mids = (int32_t*)(xlds + (SORTED ? S.mids : G.mids));     /* [2][IRT], by tile parity */
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const GroupTile T = tiles[blockIdx.x];
     const int32_t* mem = members + T.start;
@@ -982,7 +1224,13 @@ void group_i8_kernel(const int8_t* __restrict__ vectors, int d,
         mids[IRT + tid] = tile_id(1);
     }
     int32_t idn = tile_id(2);           /* ids are read two tiles ahead of their use */
-    sel_init(sel);
+    if constexpr (SORTED) {
+        int32_t* gids = (int32_t*)(xlds + S.gids);
+        for (int i = tid; i < T.count; i += XTHREADS) gids[i] = mem[i];
+        __syncthreads();
+    } else {
+        sel_init(sel);
+    }
     if (tid < XQT) {        /* query self-dots, for L2 */
         int s = 0;
         for (int w = 0; w < W; w++) {
@@ -1047,7 +1295,7 @@ void group_i8_kernel(const int8_t* __restrict__ vectors, int d,
     };
 
     const int ntile = (T.count + IRT - 1) / IRT;    /* >= 1 */
-    stage_load(0);          /* sel_init's barrier is behind the ids of tiles 0 and 1 */
+    stage_load(0);          /* the barrier above is behind the ids of tiles 0 and 1 */
     stage_store(0);
     __syncthreads();
 
@@ -1072,10 +1320,18 @@ void group_i8_kernel(const int8_t* __restrict__ vectors, int d,
             vid[r] = myvid;
             dist[r] = (DM == DM_L2) ? (float)(aa[ql[r]] - 2 * acc[r] + bb)
                                     : (float)(16129 - acc[r]);
-            if (myvid >= 0 && ql[r] < nql && myvid != qvid[ql[r]] && dist[r] <= sel.thr[ql[r]])
+            if constexpr (SORTED) {
+                if (myvid >= 0 && ql[r] < nql)
+                    ((uint32_t*)(xlds + S.mat))[ql[r] * sstride + t * IRT + wave * 32 + col] =
+                        srt_bits(dist[r], myvid != qvid[ql[r]]);
+            } else if (myvid >= 0 && ql[r] < nql && myvid != qvid[ql[r]] &&
+                       dist[r] <= sel.thr[ql[r]]) {
                 pend |= 1u << r;
+            }
         }
-        sel_append(sel, pend, dist, ql, vid);   /* ends with a barrier: the tile is free */
+        /* ends with a barrier: the tile is free */
+        if constexpr (SORTED) __syncthreads();
+        else sel_append(sel, pend, dist, ql, vid);
 
         if (t + 1 < ntile) stage_store(t + 1);
         /* tile t's ids are done with: tile t + 2's take their place */
@@ -1083,7 +1339,10 @@ void group_i8_kernel(const int8_t* __restrict__ vectors, int d,
         idn = tile_id(t + 3);
         __syncthreads();
     }
-    flush_cands(sel, 1);
+    if constexpr (SORTED)
+        srt_select_tile(xlds, S, sstride, qvid, nql, T.count, k, out_v, out_d);
+    else
+        flush_cands(sel, 1);
 }
 
 /* ------------------------------------------------------------------ *
@@ -1674,15 +1933,12 @@ static_assert(pj_lds(PJ_MAX_L, PJ_MAX_L, false, MAX_DIM, PJ_T * PJ_QS).total <= 
 
 DEV uint64_t pj_pack(float dist, int32_t id)
 {
-    uint32_t b = dist == 0.0f ? 0u : (uint32_t)__float_as_int(dist);
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((uint64_t)b << 32) | (uint32_t)id;
+    return ((uint64_t)dist_key(dist) << 32) | (uint32_t)id;
 }
 
 DEV float pj_unpack_dist(uint64_t key)
 {
-    const uint32_t b = (uint32_t)(key >> 32);
-    return __int_as_float((int)((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b));
+    return dist_unkey((uint32_t)(key >> 32));
 }
 
 /* ascending bitonic sort of P (a power of two) keys in LDS by the whole
@@ -2844,36 +3100,85 @@ int launch_exact(int vt, int dm, const DevIndex& di, const void* queries, int32_
     return (int)hipGetLastError();
 }
 
-int launch_group_knn(int vt, int dm, const void* vectors, int32_t n, int32_t dim,
-                     const int32_t* members, const GroupTile* tiles, int32_t ntiles,
-                     int32_t k, int32_t* out_v, float* out_d)
+/* the sorted selection's LDS at row stride `stride` */
+static SrtLds group_sort_lds(int vt, int32_t dim, int stride)
 {
-    if (n < 1 || dim < 1 || k < 1 || k > MAX_K || ntiles < 0 ||
-        (vt != VT_FLOAT && vt != VT_INT8) || (vt == VT_INT8 && dim > 4 * I_MAX_W))
+    return vt == VT_FLOAT ? srt_lds(f32_lds(dim).thr, FRT, stride)
+                          : srt_lds(i8_lds(dim).thr, IRT, stride);
+}
+
+int group_knn_sort_max(int vt, int32_t dim)
+{
+    if (dim < 1 || dim > MAX_DIM || (vt != VT_FLOAT && vt != VT_INT8) ||
+        (vt == VT_INT8 && dim > 4 * I_MAX_W))
+        return 0;
+    for (int s = GK_SORT_CAP; s >= 64; s -= 64)
+        if (group_sort_lds(vt, dim, s).total <= GK_LDS_MAX) return s;
+    return 0;
+}
+
+/* one of the two grouped kernels over its part of the tile table */
+template <bool SORTED>
+static int launch_group_tiles(int vt, int dm, const void* vectors, int32_t dim,
+                              const int32_t* members, const GroupTile* tiles, int32_t ntiles,
+                              int32_t k, int stride, int32_t* out_v, float* out_d)
+{
+    const dim3 grid(ntiles), block(XTHREADS);
+    const void* fn;
+    uint32_t lds;
+    if (vt == VT_FLOAT) {
+        const bool qres = f32_qstride(dim) <= FQRES_MAX;
+        auto kernel = dm == DM_L2 ? (qres ? group_f32_kernel<DM_L2, true, SORTED>
+                                          : group_f32_kernel<DM_L2, false, SORTED>)
+                                  : (qres ? group_f32_kernel<DM_COSINE, true, SORTED>
+                                          : group_f32_kernel<DM_COSINE, false, SORTED>);
+        fn = (const void*)kernel;
+        lds = SORTED ? group_sort_lds(vt, dim, stride).total
+                     : grp_lds(f32_lds(dim).total, FRT).total;
+        if (SORTED && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds) != hipSuccess)
+            return (int)hipGetLastError();
+        hipLaunchKernelGGL(kernel, grid, block, lds, nullptr, (const float*)vectors, dim,
+                           members, tiles, k, stride, out_v, out_d);
+    } else {
+        auto kernel = dm == DM_L2 ? group_i8_kernel<DM_L2, SORTED>
+                                  : group_i8_kernel<DM_COSINE, SORTED>;
+        fn = (const void*)kernel;
+        lds = SORTED ? group_sort_lds(vt, dim, stride).total
+                     : grp_lds(i8_lds(dim).total, IRT).total;
+        if (SORTED && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds) != hipSuccess)
+            return (int)hipGetLastError();
+        hipLaunchKernelGGL(kernel, grid, block, lds, nullptr, (const int8_t*)vectors, dim,
+                           members, tiles, k, stride, out_v, out_d);
+    }
+    return (int)hipGetLastError();
+}
+
+int launch_group_knn(int vt, int dm, const void* vectors, int32_t n, int32_t dim,
+                     const int32_t* members, const GroupTile* tiles, int32_t nsorted,
+                     int32_t sort_stride, int32_t nstream, int32_t k, int32_t* out_v,
+                     float* out_d)
+{
+    /* the kernels index nothing outside these bounds */
+    if (n < 1 || dim < 1 || k < 1 || k > MAX_K || nsorted < 0 || nstream < 0 ||
+        (vt != VT_FLOAT && vt != VT_INT8) || (vt == VT_INT8 && dim > 4 * I_MAX_W) ||
+        (nsorted > 0 && (sort_stride < 64 || sort_stride % 64 != 0 ||
+                         sort_stride > group_knn_sort_max(vt, dim))))
         return (int)hipErrorInvalidValue;
     const size_t total = (size_t)n * k;
     const size_t fblocks = (total + 255) / 256;
     const unsigned fill = fblocks < 65536 ? (unsigned)fblocks : 65536u;   /* grid-stride */
     hipLaunchKernelGGL(group_fill_kernel, dim3(fill), dim3(256), 0, nullptr, out_v, out_d,
                        total);
-    if (ntiles == 0) return (int)hipGetLastError();
-    const dim3 grid(ntiles), block(XTHREADS);
-    if (vt == VT_FLOAT) {
-        const bool qres = f32_qstride(dim) <= FQRES_MAX;
-        auto kernel = dm == DM_L2 ? (qres ? group_f32_kernel<DM_L2, true>
-                                          : group_f32_kernel<DM_L2, false>)
-                                  : (qres ? group_f32_kernel<DM_COSINE, true>
-                                          : group_f32_kernel<DM_COSINE, false>);
-        hipLaunchKernelGGL(kernel, grid, block, grp_lds(f32_lds(dim).total, FRT).total,
-                           nullptr, (const float*)vectors, dim, members, tiles, k, out_v,
-                           out_d);
-    } else {
-        auto kernel = dm == DM_L2 ? group_i8_kernel<DM_L2> : group_i8_kernel<DM_COSINE>;
-        hipLaunchKernelGGL(kernel, grid, block, grp_lds(i8_lds(dim).total, IRT).total,
-                           nullptr, (const int8_t*)vectors, dim, members, tiles, k, out_v,
-                           out_d);
-    }
-    return (int)hipGetLastError();
+    int err = (int)hipGetLastError();
+    if (err == 0 && nsorted > 0)
+        err = launch_group_tiles<true>(vt, dm, vectors, dim, members, tiles, nsorted, k,
+                                       sort_stride, out_v, out_d);
+    if (err == 0 && nstream > 0)
+        err = launch_group_tiles<false>(vt, dm, vectors, dim, members, tiles + nsorted,
+                                        nstream, k, 0, out_v, out_d);
+    return err;
 }
 
 int launch_rng_prune(int vt, int dm, const void* vectors, int32_t dim, const int32_t* nodes,

@@ -988,16 +988,44 @@ static bool group_ranges_ok(int64_t nmembers, const int32_t* starts, const int32
     return true;
 }
 
+/* SPTAG_AMD_GK_AUTO's rule for a group of `count` members (cap: the sorted
+ * selection's limit): every group that fits is sorted, whatever k. At 1M x
+ * 128 f32 the sorted selection was the faster one at every shape measured:
+ * leaves of 977 at k = 64 (51.6 against 190.2 ms) and k = 10 (48.8 against
+ * 86.6), of 245 at k = 64 and 10 (9.3 / 126.7, 7.9 / 70.7), of 62 at k = 10
+ * (1.9 / 43.1); profiles/group_knn_sort.txt. No shape was found where
+ * streaming wins below the cap, so k takes no part in the rule. */
+static bool group_auto_sorts(int32_t count, int32_t k, int32_t cap)
+{
+    (void)k;
+    return count <= cap;
+}
+
 /* grouped kNN into device buffers, arguments checked; `device` is current.
  * Returns once the output is complete. */
 static int group_knn_core(const void* d_vectors, int vt, int dm, int32_t n, int32_t dim,
                           const int32_t* d_members, const int32_t* starts,
-                          const int32_t* counts, int32_t ngroups, int32_t k,
-                          int32_t* d_vids, float* d_dists)
+                          const int32_t* counts, int32_t ngroups, int32_t selection,
+                          int32_t k, int32_t* d_vids, float* d_dists)
 {
+    /* which groups take the sorted selection: the tile table's first part */
+    const int32_t cap = group_knn_sort_max(vt, dim);
+    auto sorted = [&](int32_t count) {
+        return selection == SPTAG_AMD_GK_SORT ||
+               (selection == SPTAG_AMD_GK_AUTO && group_auto_sorts(count, k, cap));
+    };
+    int32_t largest = 0;
     std::vector<GroupTile> tiles;
-    for (int32_t g = 0; g < ngroups; g++)
+    for (int32_t g = 0; g < ngroups; g++) {
+        if (!sorted(counts[g])) continue;
+        if (counts[g] > cap) return SPTAG_AMD_ERR_PARAM;    /* SORT alone gets here */
+        largest = std::max(largest, counts[g]);
         for (int32_t q0 = 0; q0 < counts[g]; q0 += EXACT_QT)
+            tiles.push_back({starts[g], counts[g], q0});
+    }
+    const int32_t nsorted = (int32_t)tiles.size();
+    for (int32_t g = 0; g < ngroups; g++)
+        for (int32_t q0 = 0; q0 < counts[g] && !sorted(counts[g]); q0 += EXACT_QT)
             tiles.push_back({starts[g], counts[g], q0});
     DevBuf d_tiles;
     if (!tiles.empty()) {
@@ -1005,8 +1033,8 @@ static int group_knn_core(const void* d_vectors, int vt, int dm, int32_t n, int3
         if (rc != SPTAG_AMD_OK) return rc;
     }
     int err = launch_group_knn(vt, dm, d_vectors, n, dim, d_members,
-                               d_tiles.as<GroupTile>(), (int32_t)tiles.size(), k, d_vids,
-                               d_dists);
+                               d_tiles.as<GroupTile>(), nsorted, (largest + 63) & ~63,
+                               (int32_t)tiles.size() - nsorted, k, d_vids, d_dists);
     if (err != 0) {
         fprintf(stderr, "sptag_amd: group knn launch failed %d\n", err);
         return SPTAG_AMD_ERR_INTERNAL;
@@ -1015,29 +1043,63 @@ static int group_knn_core(const void* d_vectors, int vt, int dm, int32_t n, int3
     return SPTAG_AMD_OK;
 }
 
+static bool group_selection_ok(int32_t selection)
+{
+    return selection == SPTAG_AMD_GK_STREAM || selection == SPTAG_AMD_GK_SORT ||
+           selection == SPTAG_AMD_GK_AUTO;
+}
+
+int32_t sptag_amd_group_knn_sort_max(int valuetype, int32_t dim)
+{
+    if (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) return 0;
+    return group_knn_sort_max(valuetype, dim);
+}
+
+int sptag_amd_group_knn_sel_device(int device, const void* d_vectors, int valuetype,
+                                   int distmethod, int32_t n, int32_t dim,
+                                   const int32_t* d_members, int32_t nmembers,
+                                   const int32_t* starts, const int32_t* counts,
+                                   int32_t ngroups, int32_t selection, int32_t k,
+                                   int32_t* d_out_vids, float* d_out_dists)
+{
+    if (!d_vectors || !d_members || !d_out_vids || !d_out_dists || n < 1 || dim < 1 ||
+        dim > MAX_DIM || (valuetype != VT_FLOAT && valuetype != VT_INT8) ||
+        (distmethod != DM_L2 && distmethod != DM_COSINE) ||
+        (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) ||
+        !group_selection_ok(selection) ||
+        !group_ranges_ok(nmembers, starts, counts, ngroups, k))
+        return SPTAG_AMD_ERR_PARAM;
+    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
+    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
+    return group_knn_core(d_vectors, valuetype, distmethod, n, dim, d_members, starts, counts,
+                          ngroups, selection, k, d_out_vids, d_out_dists);
+}
+
 int sptag_amd_group_knn_device(int device, const void* d_vectors, int valuetype,
                                int distmethod, int32_t n, int32_t dim,
                                const int32_t* d_members, int32_t nmembers,
                                const int32_t* starts, const int32_t* counts, int32_t ngroups,
                                int32_t k, int32_t* d_out_vids, float* d_out_dists)
 {
-    if (!d_vectors || !d_members || !d_out_vids || !d_out_dists || n < 1 || dim < 1 ||
-        dim > MAX_DIM || (valuetype != VT_FLOAT && valuetype != VT_INT8) ||
-        (distmethod != DM_L2 && distmethod != DM_COSINE) ||
-        (valuetype == VT_INT8 && (int64_t)dim * 254 * 254 >= (1ll << 24)) ||
-        !group_ranges_ok(nmembers, starts, counts, ngroups, k))
-        return SPTAG_AMD_ERR_PARAM;
-    if (!sptag_amd_gpu_available()) return SPTAG_AMD_ERR_NOGPU;
-    HIP_OR_FAIL(hipSetDevice(device), SPTAG_AMD_ERR_NOGPU);
-    return group_knn_core(d_vectors, valuetype, distmethod, n, dim, d_members, starts, counts,
-                          ngroups, k, d_out_vids, d_out_dists);
+    return sptag_amd_group_knn_sel_device(device, d_vectors, valuetype, distmethod, n, dim,
+                                          d_members, nmembers, starts, counts, ngroups,
+                                          SPTAG_AMD_GK_STREAM, k, d_out_vids, d_out_dists);
 }
 
 int sptag_amd_group_knn(SptagAmdIndex* ix, const int32_t* members, int32_t nmembers,
                         const int32_t* starts, const int32_t* counts, int32_t ngroups,
                         int32_t k, int32_t* out_vids, float* out_dists)
 {
-    if (!ix || !members || !out_vids || !out_dists ||
+    return sptag_amd_group_knn_sel(ix, members, nmembers, starts, counts, ngroups,
+                                   SPTAG_AMD_GK_STREAM, k, out_vids, out_dists);
+}
+
+int sptag_amd_group_knn_sel(SptagAmdIndex* ix, const int32_t* members, int32_t nmembers,
+                            const int32_t* starts, const int32_t* counts, int32_t ngroups,
+                            int32_t selection, int32_t k, int32_t* out_vids,
+                            float* out_dists)
+{
+    if (!ix || !members || !out_vids || !out_dists || !group_selection_ok(selection) ||
         !group_ranges_ok(nmembers, starts, counts, ngroups, k))
         return SPTAG_AMD_ERR_PARAM;
     if (!sptag_amd_gpu_available() || !ix->d_vectors) return SPTAG_AMD_ERR_NOGPU;
@@ -1057,8 +1119,8 @@ int sptag_amd_group_knn(SptagAmdIndex* ix, const int32_t* members, int32_t nmemb
     if (rc != SPTAG_AMD_OK) return rc;
     if ((rc = out.ensure(total)) != SPTAG_AMD_OK) return rc;
     rc = group_knn_core(ix->d_vectors.as(), ix->vt, ix->dm, ix->n, ix->dim,
-                        d_members.as<int32_t>(), starts, counts, ngroups, k, out.vids(),
-                        out.dists());
+                        d_members.as<int32_t>(), starts, counts, ngroups, selection, k,
+                        out.vids(), out.dists());
     return rc != SPTAG_AMD_OK ? rc : out.download(out_vids, out_dists, total);
 }
 
